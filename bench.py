@@ -14,7 +14,13 @@ A "step" = one fused decode+aggregate pass over the whole shard (resident
 in HBM) plus, for N>1, the cross-shard RCCL GROUP BY merge.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode walk|random]
+                       [--dump-outputs DIR] [--full]
 For N>1 launch via torch.distributed.run (one rank per GPU).
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --full additionally times the CPU oracle baseline (the
+`cpu_baseline` entry of the result line). --dump-outputs DIR writes the
+rows the last timed step returned as DIR/<field>.npy (float64).
 """
 
 import argparse
@@ -81,6 +87,26 @@ def cpu_baseline_leg(mode, mode_name):
     }
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # stay well under 64 MB in all
+
+
+def dump_outputs(rows, out_dir):
+    """Write the rows a caller of the timed path received in the last timed
+    step, one float64 array per row field (DIR/<field>.npy; padding
+    skipped). Outputs too large for the budget are cut to a fixed, seeded
+    sample of rows (ascending row order), the same from run to run."""
+    fields = [f for f in rows.dtype.names if not f.startswith("_")]
+    max_rows = DUMP_BUDGET_BYTES // (8 * len(fields))
+    if len(rows) > max_rows:
+        rng = np.random.default_rng(SEED)
+        idx = np.sort(rng.choice(len(rows), size=max_rows, replace=False))
+        rows = rows[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(out_dir, f + ".npy"),
+                np.ascontiguousarray(rows[f], dtype=np.float64))
+
+
 def read_traffic_file():
     """PMC-measured HBM bytes per scan launch, if a committed measurement
     exists (profiles/hbm_traffic.json, written from rocprofv3 --pmc runs —
@@ -118,7 +144,16 @@ def main():
                     help="tag groups for --query tags")
     ap.add_argument("--pts", type=int, default=1000)
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU oracle baseline (cpu_baseline "
+                         "in the result line); a plain run only measures "
+                         "the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last "
+                         "timed step returned as DIR/<field>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import binding as orc  # oracle: data authoring + cpu_baseline only
     import opengemini_amd as gx
@@ -290,6 +325,9 @@ def main():
     if rank != 0:
         return
 
+    if args.dump_outputs:
+        dump_outputs(rows, args.dump_outputs)
+
     # roofline: dominant kernel = fused decode+reduce (k_scan_fast).
     # achieved = ALGORITHMIC bytes per launch (compressed data+time segment
     # bytes — SURVEY.md §8d: B_alg/pt = C_ts + C_val; outputs negligible)
@@ -305,8 +343,8 @@ def main():
         traffic = tf.get("bytes_per_launch")
 
     cpu_baseline = None
-    if (not args.skip_cpu_baseline and args.query == "mean" and n_gpus == 1
-            and args.mode != "int"):
+    if (args.full and not args.skip_cpu_baseline and args.query == "mean"
+            and n_gpus == 1 and args.mode != "int"):
         # contract: cpu_baseline on rank 0 at N=1 only
         cpu_baseline = cpu_baseline_leg(gen_mode, args.mode)
 
