@@ -152,6 +152,22 @@ int gemx_scan_agg_grouped(gemx_shard *, int64_t start_time, int64_t end_time,
                           gemx_agg_row *out_host, uint64_t cap, uint64_t *n_out,
                           gemx_query_stats *stats);
 
+/* Wave-fold coverage of the shard's last grouped (all-series GROUP BY
+ * time) query. Waves of 64 aligned gorilla segments — same (t0, dt, rows),
+ * series strictly time-disjoint — are reduced inside the scan kernel and
+ * skip the per-(segment,window) partial round trip; results are identical
+ * to the unfolded path (float sum within 1e-9). folded_segments of
+ * scanned_segments in-range segments took that path. *redone is 1 when a
+ * folded window started on NaN and the query was run again unfolded (the
+ * plan then stays unfolded). Shards small enough to run the sub-segment
+ * split (fewer than 65536 gorilla segments) keep the split and do not fold.
+ * Environment, read at attach and kept per shard: GEMX_DISABLE_FOLD turns
+ * folding off; GEMX_FOLD_UNDERFILLED folds on split-sized shards too (an
+ * A/B and test switch — measured slower there). Any out pointer may be
+ * NULL. */
+int gemx_fold_stats(gemx_shard *, uint64_t *folded_segments,
+                    uint64_t *scanned_segments, uint32_t *redone);
+
 /* value-predicate pushdown (config #3): lib/binaryfilterfunc compare
  * kernels (eval_generator.gen.go:31+) with FilterByField semantics
  * (immutable/location.go:309) — rows failing the predicate (and nil rows)

@@ -33,6 +33,8 @@
 #include <stdlib.h>
 #include <math.h>
 #include <vector>
+#include <map>
+#include <tuple>
 #include <string>
 #include <algorithm>
 #include <chrono>
@@ -941,7 +943,9 @@ struct SeriesQ {
 
 struct DevErr {
   int code; /* first error wins */
-  unsigned int _pad;
+  unsigned int fold_nan; /* folded gorilla waves: windows whose running min
+                            started as NaN (the host redoes the query
+                            unfolded when non-zero) */
   unsigned long long gaps; /* gap rows written by the merge kernels; the
                               host skips its compaction scan when zero */
 };
@@ -949,6 +953,19 @@ struct DevErr {
 __device__ __forceinline__ void set_err(DevErr *e, int code) {
   atomicCAS(&e->code, 0, code);
 }
+
+/* cross-series group accumulator (semantics documented at gacc_merge) */
+struct GAcc {
+  int64_t count;
+  gemx_val sum, minv, maxv, firstv, lastv;
+  int64_t min_t, max_t, first_t, last_t;
+  /* series-order index of each candidate: the reference processes series
+   * in sid order and ties keep the first-processed — the tree reduce
+   * resolves full ties by the smaller source index */
+  uint32_t min_src, max_src, first_src, last_src;
+  uint32_t active; /* bit1 sum, bit2 min, bit3 max, bit4 first, bit5 last */
+  uint32_t used;
+};
 
 /* accumulate one (t, value, valid) row stream into per-window partials.
  * Shared by fast path (no nils) with streaming times/values. */
@@ -1270,6 +1287,81 @@ __global__ void __launch_bounds__(256) k_scan_fast(
 #undef GEMX_DECODE_ONE
 }
 
+/* ---- wave fold (grouped scans over aligned gorilla waves) ----
+ *
+ * Per-wave entry of the plan's fold table, indexed by launch-list
+ * position / 64. fidx < 0: the wave runs the per-segment Partial path. */
+struct FoldWave {
+  int32_t fidx;    /* column in the [window][folded wave] GAcc array */
+  uint32_t tab;    /* offset of this wave's row-boundary table */
+  uint32_t n_wins; /* windows covered; table holds n_wins + 1 entries */
+  uint32_t wrel;   /* first window, relative to the plan's W0 */
+};
+
+/* one lane's window result inside a folded wave; times travel as row
+ * indices because (t0, dt) are wave-uniform */
+struct FoldLane {
+  double sum, mn, mx, firstv, lastv;
+  uint32_t min_row, max_row;
+  uint32_t min_src, max_src, fl_src; /* series index (SegQ.series_idx) */
+};
+
+__device__ __forceinline__ int64_t d_rfl64(int64_t v) {
+  uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double d_shx_f64(double v, int m) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __shfl_xor(lo, m, 64);
+  hi = __shfl_xor(hi, m, 64);
+  return __hiloint2double(hi, lo);
+}
+
+/* Fixed xor-butterfly over the wave reproducing gacc_merge's algebra for
+ * aligned lanes: sum adds (fixed order, so run-to-run identical; a + b is
+ * commutative, so every lane ends with the same bits); min/max compare by
+ * (value, earlier row, smaller series index); first/last tie on time
+ * across the wave and take the smaller series index. Lanes >= nvalid are
+ * absent and never win. All 64 lanes must be active. Written as a device
+ * function so other lane-per-segment kernels can reuse it. */
+__device__ __forceinline__ void fold_wave_reduce(FoldLane &a, uint32_t nvalid) {
+  const uint32_t lane = threadIdx.x & 63;
+  bool lu = lane < nvalid;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    /* the partner holds the result of its aligned m-lane block, which is
+     * live when the block's first lane is present */
+    const bool ru = ((lane ^ (uint32_t)m) & ~(uint32_t)(m - 1)) < nvalid;
+    const double rsum = d_shx_f64(a.sum, m);
+    const double rmn = d_shx_f64(a.mn, m);
+    const double rmx = d_shx_f64(a.mx, m);
+    const double rfv = d_shx_f64(a.firstv, m);
+    const double rlv = d_shx_f64(a.lastv, m);
+    const uint32_t rminr = (uint32_t)__shfl_xor((int)a.min_row, m, 64);
+    const uint32_t rmaxr = (uint32_t)__shfl_xor((int)a.max_row, m, 64);
+    const uint32_t rmins = (uint32_t)__shfl_xor((int)a.min_src, m, 64);
+    const uint32_t rmaxs = (uint32_t)__shfl_xor((int)a.max_src, m, 64);
+    const uint32_t rfls = (uint32_t)__shfl_xor((int)a.fl_src, m, 64);
+    if (ru) {
+      const bool tmin =
+          !lu || rmn < a.mn ||
+          (rmn == a.mn &&
+           (rminr < a.min_row || (rminr == a.min_row && rmins < a.min_src)));
+      const bool tmax =
+          !lu || rmx > a.mx ||
+          (rmx == a.mx &&
+           (rmaxr < a.max_row || (rmaxr == a.max_row && rmaxs < a.max_src)));
+      const bool tfl = !lu || rfls < a.fl_src;
+      a.sum = lu ? a.sum + rsum : rsum;
+      if (tmin) { a.mn = rmn; a.min_row = rminr; a.min_src = rmins; }
+      if (tmax) { a.mx = rmx; a.max_row = rmaxr; a.max_src = rmaxs; }
+      if (tfl) { a.firstv = rfv; a.lastv = rlv; a.fl_src = rfls; }
+      lu = true;
+    }
+  }
+}
+
 /* ---------------- branchless Gorilla grid kernel ----------------
  *
  * The headline walk/random path: one lane per nil-free, const-delta-time,
@@ -1299,37 +1391,12 @@ __global__ void __launch_bounds__(256) k_scan_fast(
  *  - uvnan is OR-folded into a flag checked once per segment: a
  *    mid-stream uvnan (corrupt) or a missing terminator raises
  *    GEMX_E_DECODE after the fact instead of branching per record.
+ *
+ * FOLD adds the grouped wave-fold path (see fold_wave_reduce above): waves
+ * the plan marked aligned reduce each window across their 64 lanes and
+ * write one GAcc per (window, wave) instead of 64 Partials. The FOLD=false
+ * instantiation is the per-segment kernel unchanged.
  */
-__global__ void __launch_bounds__(256) k_scan_grid_gor(
-    const uint64_t *__restrict__ arena, uint64_t arena_words,
-    const GorDesc *__restrict__ gors, const gemx_seg_desc *__restrict__ descs,
-    const SegQ *__restrict__ segq, const uint32_t *__restrict__ seg_ids,
-    uint32_t nseg_ids, Partial *__restrict__ partials, int64_t interval,
-    int64_t offset, DevErr *err) {
-  uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  for (uint32_t li = gid; li < nseg_ids; li += gridDim.x * blockDim.x) {
-    uint32_t si = seg_ids[li];
-    const gemx_seg_desc d = descs[si];
-    const SegQ sq = segq[si];
-    if (sq.n_wins == 0) continue;
-
-    const GorDesc g = gors[si];
-    const int64_t t0c = g.t0, dtc = g.dt;
-    const int rows = (int)d.rows;
-    uint64_t g_val = g.first_val;
-    if (g_val == UVNAN) { /* empty stream but rows > 0 */
-      set_err(err, GEMX_E_DECODE);
-      return;
-    }
-    GorA br;
-    br.init(arena, g.arena_base);
-    (void)arena_words;
-    uint32_t g_mean = 64, g_trail = 0;
-    uint64_t bad = 0; /* count of uvnan hits; exactly 1 (terminator) is legal */
-
-    Partial *base = partials + sq.partial_base;
-    for (uint32_t k = 0; k < sq.n_wins; k++) base[k].has_rows = 0;
-
 /* one record, straight-line: funnel-extract the 13-bit header
  * (ctrl0+ctrl1+5 lead+6 meaningful) and the significant bits from the
  * 256-bit window, advance the bit cursor, then shift the window by
@@ -1356,6 +1423,130 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
       br.bp = (int)(np & 63);                                                  \
       br.step(adv);                                                          \
     } while (0)
+
+template <bool FOLD>
+__global__ void __launch_bounds__(256) k_scan_grid_gor(
+    const uint64_t *__restrict__ arena, uint64_t arena_words,
+    const GorDesc *__restrict__ gors, const gemx_seg_desc *__restrict__ descs,
+    const SegQ *__restrict__ segq, const uint32_t *__restrict__ seg_ids,
+    uint32_t nseg_ids, Partial *__restrict__ partials, int64_t interval,
+    int64_t offset, DevErr *err, const FoldWave *__restrict__ fwaves,
+    const uint32_t *__restrict__ fbounds, GAcc *__restrict__ fold_out,
+    uint32_t n_fold) {
+  uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  /* FOLD keeps the absent lanes of the last wave in the loop: a folded
+   * wave reduces across all 64 lanes */
+  for (uint32_t li = gid; FOLD ? ((li & ~63u) < nseg_ids) : (li < nseg_ids);
+       li += gridDim.x * blockDim.x) {
+    if (FOLD) {
+      const FoldWave fw = fwaves[li >> 6];
+      const int fidx = __builtin_amdgcn_readfirstlane(fw.fidx);
+      if (fidx >= 0) {
+        /* ---- folded wave: the 64 segments share (t0, dt, rows), so every
+         * lane crosses each window boundary on the same trip. No Partial
+         * is cleared or stored; the wave reduces each window in registers
+         * and lane 0 writes one GAcc per (window, wave). Row boundaries
+         * come from the plan's host-built table (no 64-bit division). */
+        const uint32_t nvalid = min(64u, nseg_ids - (li & ~63u));
+        const bool valid = li < nseg_ids;
+        /* absent lanes decode lane 0's stream (in-bounds, keeps control
+         * flow wave-uniform) and are masked out of the reduce */
+        const uint32_t si = seg_ids[valid ? li : (li & ~63u)];
+        const GorDesc g = gors[si];
+        const uint32_t src = segq[si].series_idx;
+        const int64_t t0c = d_rfl64(g.t0), dtc = d_rfl64(g.dt);
+        const uint32_t nw = (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.n_wins);
+        const uint32_t *bt =
+            fbounds + (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.tab);
+        GAcc *orow = fold_out +
+                     (uint64_t)__builtin_amdgcn_readfirstlane((int)fw.wrel) * n_fold +
+                     (uint32_t)fidx;
+        uint64_t g_val = g.first_val;
+        if (g_val == UVNAN) set_err(err, GEMX_E_DECODE); /* decode stays
+            inside the arena pad; the result is discarded */
+        GorA br;
+        br.init(arena, g.arena_base);
+        uint32_t g_mean = 64, g_trail = 0;
+        uint64_t bad = 0;
+        uint32_t i = 0;
+        for (uint32_t k = 0; k < nw; k++, orow += n_fold) {
+          const uint32_t gend = bt[k + 1];
+          if (gend <= i) continue; /* empty window: slot stays unused */
+          if (i != 0) GOR_NEXT();
+          double fv;
+          memcpy(&fv, &g_val, 8);
+          FoldLane a;
+          a.sum = fv;
+          a.mn = fv;
+          a.mx = fv;
+          a.firstv = fv;
+          a.lastv = fv;
+          a.min_row = i;
+          a.max_row = i;
+          for (uint32_t r = i + 1; r < gend; r++) {
+            GOR_NEXT();
+            double v;
+            memcpy(&v, &g_val, 8);
+            a.sum += v;
+            if (a.mn > v) { a.mn = v; a.min_row = r; }
+            if (a.mx < v) { a.mx = v; a.max_row = r; }
+            a.lastv = v;
+          }
+          /* a NaN first value pins min/max and makes the merge tree
+           * order-dependent: flag it, the host redoes the query unfolded */
+          if (valid && a.mn != a.mn) atomicAdd(&err->fold_nan, 1u);
+          a.min_src = a.max_src = a.fl_src = src;
+          fold_wave_reduce(a, nvalid);
+          if ((threadIdx.x & 63) == 0) {
+            GAcc o;
+            o.count = (int64_t)(gend - i) * nvalid;
+            o.sum.f = a.sum;
+            o.minv.f = a.mn;
+            o.maxv.f = a.mx;
+            o.firstv.f = a.firstv;
+            o.lastv.f = a.lastv;
+            o.min_t = t0c + (int64_t)a.min_row * dtc;
+            o.max_t = t0c + (int64_t)a.max_row * dtc;
+            o.first_t = t0c + (int64_t)i * dtc;
+            o.last_t = t0c + (int64_t)(gend - 1) * dtc;
+            o.min_src = a.min_src;
+            o.max_src = a.max_src;
+            o.first_src = a.fl_src;
+            o.last_src = a.fl_src;
+            o.active = 2 | 4 | 8 | 16 | 32;
+            o.used = 1;
+            *orow = o;
+          }
+          i = gend;
+        }
+        GOR_NEXT();
+        if (bad != 1 || g_val != UVNAN) set_err(err, GEMX_E_DECODE);
+        continue;
+      }
+      if (li >= nseg_ids) continue;
+    }
+    uint32_t si = seg_ids[li];
+    const gemx_seg_desc d = descs[si];
+    const SegQ sq = segq[si];
+    if (sq.n_wins == 0) continue;
+
+    const GorDesc g = gors[si];
+    const int64_t t0c = g.t0, dtc = g.dt;
+    const int rows = (int)d.rows;
+    uint64_t g_val = g.first_val;
+    if (g_val == UVNAN) { /* empty stream but rows > 0 */
+      set_err(err, GEMX_E_DECODE);
+      return;
+    }
+    GorA br;
+    br.init(arena, g.arena_base);
+    (void)arena_words;
+    uint32_t g_mean = 64, g_trail = 0;
+    uint64_t bad = 0; /* count of uvnan hits; exactly 1 (terminator) is legal */
+
+    Partial *base = partials + sq.partial_base;
+    for (uint32_t k = 0; k < sq.n_wins; k++) base[k].has_rows = 0;
+
 
     int first_pending = 1;
     int i = 0;
@@ -1418,9 +1609,10 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
       set_err(err, GEMX_E_DECODE);
       return;
     }
-#undef GOR_NEXT
   }
 }
+
+#undef GOR_NEXT
 
 /* ---------------- gorilla sub-segment kernels (config #1 underfill) ----
  *
@@ -2438,10 +2630,11 @@ __global__ void __launch_bounds__(256) k_scan_general(
  * (series_agg_func.gen.go:44-274); returns 0 when the window has no rows
  * in this series. Shared by the per-series row kernel and the fused
  * grouped path. */
-template <int COLTYPE>
+template <int COLTYPE, bool SKIPF = false>
 __device__ int merge_series_window(const SeriesQ &s, const SegQ *__restrict__ segq,
                                    const Partial *__restrict__ partials, int64_t w,
-                                   gemx_agg_row *out) {
+                                   gemx_agg_row *out,
+                                   const uint8_t *__restrict__ seg_folded = nullptr) {
   int active[6] = {0, 0, 0, 0, 0, 0};
   gemx_val av[6];
   int64_t at[6], nt[6];
@@ -2457,6 +2650,9 @@ __device__ int merge_series_window(const SeriesQ &s, const SegQ *__restrict__ se
   for (uint32_t si = flo; si < b && segq[si].w_first <= w; si++) {
     const SegQ q = segq[si];
     if (w < q.w_first || w >= q.w_first + (int64_t)q.n_wins) continue;
+    /* grouped fold: this segment's windows live in the wave-fold array,
+     * its Partial slots were never written */
+    if (SKIPF && seg_folded[si]) continue;
     const Partial p = partials[q.partial_base + (w - q.w_first)];
     if (!p.has_rows) continue;
     any = 1;
@@ -2562,17 +2758,8 @@ __global__ void __launch_bounds__(256) k_merge(
  *  the series deterministically, then an LDS tree with left-precedence
  *  merges thread partials — bit-exact for count/min/max/first/last, fixed
  *  reassociation for float sum (within the 1e-9 contract). */
-struct GAcc {
-  int64_t count;
-  gemx_val sum, minv, maxv, firstv, lastv;
-  int64_t min_t, max_t, first_t, last_t;
-  /* series-order index of each candidate: the reference processes series
-   * in sid order and ties keep the first-processed — the tree reduce
-   * resolves full ties by the smaller source index */
-  uint32_t min_src, max_src, first_src, last_src;
-  uint32_t active; /* bit1 sum, bit2 min, bit3 max, bit4 first, bit5 last */
-  uint32_t used;
-};
+/* struct GAcc: defined with the scan kernels above (the folded gorilla
+ * scan writes it directly) */
 
 template <int COLTYPE>
 __device__ __forceinline__ void gacc_row(GAcc *a, const gemx_agg_row *r,
@@ -2713,12 +2900,16 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
   }
 }
 
-template <int COLTYPE>
+/* FOLD: `sel` lists (ascending) the nseries series that still own a
+ * non-folded in-range segment; folded segments are skipped and the source
+ * index stays the series' own position */
+template <int COLTYPE, bool FOLD = false>
 __global__ void __launch_bounds__(256) k_group_p1(
     const SeriesQ *__restrict__ series, uint32_t nseries,
     const SegQ *__restrict__ segq, const Partial *__restrict__ partials,
     GAcc *__restrict__ gtmp, int64_t W0, uint32_t n_gwins, uint32_t split,
-    uint32_t per_chunk) {
+    uint32_t per_chunk, const uint32_t *__restrict__ sel = nullptr,
+    const uint8_t *__restrict__ seg_folded = nullptr) {
   __shared__ GAcc sh[256];
   for (uint32_t bb = blockIdx.x; bb < n_gwins * split; bb += gridDim.x) {
     uint32_t wb = bb / split, c = bb % split;
@@ -2728,13 +2919,16 @@ __global__ void __launch_bounds__(256) k_group_p1(
     if (g1 > nseries) g1 = nseries;
     GAcc a;
     memset(&a, 0, sizeof(a));
-    for (uint32_t g = g0 + threadIdx.x; g < g1; g += blockDim.x) {
+    for (uint32_t gi = g0 + threadIdx.x; gi < g1; gi += blockDim.x) {
+      const uint32_t g = FOLD ? sel[gi] : gi;
       const SeriesQ s = series[g];
       int64_t local = w - s.w_min;
       if (local < 0 || local >= (int64_t)s.n_wins) continue;
       gemx_agg_row r;
       memset(&r, 0, sizeof(r));
-      if (!merge_series_window<COLTYPE>(s, segq, partials, w, &r)) continue;
+      if (!merge_series_window<COLTYPE, FOLD>(s, segq, partials, w, &r,
+                                              seg_folded))
+        continue;
       gacc_row<COLTYPE>(&a, &r, g);
     }
     sh[threadIdx.x] = a;
@@ -2753,7 +2947,8 @@ template <int COLTYPE>
 __global__ void __launch_bounds__(256) k_group_p2(
     const GAcc *__restrict__ gtmp, uint32_t split, gemx_agg_row *__restrict__ out,
     int64_t W0, uint32_t n_gwins, int64_t interval, int64_t offset,
-    int64_t q_start, int keep_empty, DevErr *__restrict__ err) {
+    int64_t q_start, int keep_empty, DevErr *__restrict__ err,
+    const GAcc *__restrict__ fold = nullptr, uint32_t n_fold = 0) {
   __shared__ GAcc sh[256];
   for (uint32_t wb = blockIdx.x; wb < n_gwins; wb += gridDim.x) {
     int64_t w = W0 + (int64_t)wb;
@@ -2761,6 +2956,10 @@ __global__ void __launch_bounds__(256) k_group_p2(
     memset(&a, 0, sizeof(a));
     for (uint32_t c = threadIdx.x; c < split; c += blockDim.x)
       gacc_merge<COLTYPE>(&a, &gtmp[wb * split + c]);
+    /* wave-fold entries of this window ([window][folded wave]; waves that
+     * do not cover the window read as unused) */
+    for (uint32_t c = threadIdx.x; c < n_fold; c += blockDim.x)
+      gacc_merge<COLTYPE>(&a, &fold[(uint64_t)wb * n_fold + c]);
     sh[threadIdx.x] = a;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -4048,6 +4247,18 @@ struct QueryPlan {
   uint32_t gsplit = 1, gper_chunk = 1;
   int64_t W0 = 0;
   uint64_t n_gwins = 0;
+  /* grouped wave fold (aligned gorilla waves reduce in-kernel; see
+   * k_scan_grid_gor<true>). Built with the plan, used only by launches
+   * that are group_all with no tag query and no filter; every other
+   * query on this plan runs the per-segment Partial path. */
+  FoldWave *d_fwaves = nullptr;    /* per gorilla-launch wave */
+  uint32_t *d_fbounds = nullptr;   /* deduplicated row-boundary tables */
+  void *d_fold = nullptr;          /* GAcc[n_gwins][n_fold_waves] */
+  uint8_t *d_seg_folded = nullptr; /* per segment */
+  uint32_t *d_p1_sel = nullptr;    /* series with a non-folded segment */
+  uint32_t n_fold_waves = 0, n_p1_sel = 0, fsplit = 1, fper_chunk = 1;
+  uint64_t fold_segs = 0, scan_segs = 0;
+  bool fold_off = false; /* set after a NaN redo: stay unfolded */
 };
 
 /* cached GROUP BY tag device state (sid→group permutation + chunk table;
@@ -4141,6 +4352,21 @@ struct gemx_shard {
     uint32_t start, count;
   };
   std::vector<SeriesRange> series_ranges;
+  /* wave-fold eligibility (attach-time): per series, segments strictly
+   * time-disjoint (max_time[i] < min_time[i+1]); overlapping segments are
+   * legal input and are never folded */
+  std::vector<char> ser_disjoint;
+  bool fold_disabled = false; /* GEMX_DISABLE_FOLD at attach */
+  bool fold_underfilled = false; /* GEMX_FOLD_UNDERFILLED at attach: fold
+      even where the sub-segment split would run (measured slower there;
+      an A/B and test switch) */
+  struct FoldQ {
+    bool folded = false;
+    int keep_empty = 0;
+    uint64_t cap = 0;
+  } fold_q[2]; /* per slot: what scan_deliver needs to redo unfolded */
+  uint64_t last_fold_folded = 0, last_fold_scanned = 0;
+  uint32_t last_fold_redo = 0;
   uint64_t total_rows_scanned; /* Σ rows */
   uint64_t total_compressed_bytes = 0; /* Σ data+time segment bytes (cached:
       summing 1M descriptors per query in scan_deliver cost ~1 ms/step on
@@ -4224,6 +4450,11 @@ static void free_plan(QueryPlan &p) {
   if (p.d_subq) (void)hipFree(p.d_subq);
   if (p.d_subpart) (void)hipFree(p.d_subpart);
   if (p.d_fasts_q) (void)hipFree(p.d_fasts_q);
+  if (p.d_fwaves) (void)hipFree(p.d_fwaves);
+  if (p.d_fbounds) (void)hipFree(p.d_fbounds);
+  if (p.d_fold) (void)hipFree(p.d_fold);
+  if (p.d_seg_folded) (void)hipFree(p.d_seg_folded);
+  if (p.d_p1_sel) (void)hipFree(p.d_p1_sel);
   p = QueryPlan();
 }
 
@@ -4897,6 +5128,14 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
     }
   }
 
+  s->fold_disabled = getenv("GEMX_DISABLE_FOLD") != nullptr;
+  s->fold_underfilled = getenv("GEMX_FOLD_UNDERFILLED") != nullptr;
+  s->ser_disjoint.assign(s->series_ranges.size(), 1);
+  for (size_t g = 0; g < s->series_ranges.size(); g++) {
+    const auto &r = s->series_ranges[g];
+    for (uint32_t i = r.start; i + 1 < r.start + r.count; i++)
+      if (descs[i].max_time >= descs[i + 1].min_time) s->ser_disjoint[g] = 0;
+  }
   {
     int grc = build_gor_arena(s, hb);
     if (grc != 0) {
@@ -5066,17 +5305,20 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                      gemx_query_stats *stats, const char *skip_series = nullptr,
                      const TagQuery *tagq = nullptr, int async_begin = 0,
                      const uint8_t *xbm = nullptr,
-                     const uint64_t *xbase = nullptr, int keep_empty = 0) {
+                     const uint64_t *xbase = nullptr, int keep_empty = 0,
+                     int redo_slot = -1) {
   if (!s) return GEMX_E_INVALID;
+  /* redo_slot >= 0: unfolded redo from scan_deliver — reuses the finished
+   * slot and may run while the other slot is still in flight */
   if (async_begin && (tagq || skip_series)) {
     seterr("async begin supports plain/grouped scans only");
     return GEMX_E_INVALID;
   }
-  if (async_begin && s->pend_count >= 2) {
+  if (redo_slot < 0 && async_begin && s->pend_count >= 2) {
     seterr("two queries already in flight: call gemx_scan_agg_finish");
     return GEMX_E_INVALID;
   }
-  if (!async_begin && s->pend_count > 0) {
+  if (redo_slot < 0 && !async_begin && s->pend_count > 0) {
     seterr("async queries in flight: call gemx_scan_agg_finish first");
     return GEMX_E_INVALID;
   }
@@ -5332,6 +5574,115 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
       HIP_CHECK(hipMalloc(&P.d_gtmp, sizeof(GAcc) * (P.n_gwins ? P.n_gwins : 1) *
                                          P.gsplit));
     }
+    /* grouped wave fold: classify each run of 64 gorilla-launch entries
+     * (one wave; the launch list is in arena slot order). A wave folds
+     * when its members share (t0, dt, rows) and each member's series is
+     * strictly time-disjoint with every in-range segment an unclipped
+     * gorilla-list segment — then merging per wave first is exact (see
+     * DESIGN.md §5). Row boundaries per window are computed here so the
+     * folded kernel path has no 64-bit division. */
+    if (interval > 0 && !skip_series && !xbm && !s->fold_disabled &&
+        (!P.d_subq || s->fold_underfilled) && s->col_type == GEMX_TYPE_FLOAT &&
+        P.n_gwins > 0 && P.sq.size() > 32) {
+      const std::vector<uint32_t> &gl = any_clip ? fast_gorq : s->fast_gor_ids;
+      std::vector<char> in_gl(nsegs, 0);
+      for (auto id : gl) in_gl[id] = 1;
+      std::vector<char> ser_ok(P.sq.size(), 0);
+      for (size_t g = 0; g < P.sq.size(); g++) {
+        char ok = s->ser_disjoint[g];
+        const auto &r = s->series_ranges[g];
+        for (uint32_t i = r.start; ok && i < r.start + r.count; i++)
+          if (P.segq[i].n_wins && !in_gl[i]) ok = 0;
+        ser_ok[g] = ok;
+      }
+      std::vector<FoldWave> fw((gl.size() + 63) / 64);
+      std::vector<uint32_t> bounds;
+      std::map<std::tuple<int64_t, int64_t, uint32_t>, uint32_t> tabs;
+      std::vector<uint8_t> folded(nsegs ? nsegs : 1, 0);
+      uint32_t nfold = 0;
+      for (size_t wv = 0; wv < fw.size(); wv++) {
+        const size_t a = wv * 64, b = std::min(a + 64, gl.size());
+        const uint32_t f0 = gl[a];
+        const int64_t t0 = s->h_gor[f0].t0, dt = s->h_gor[f0].dt;
+        const uint32_t rows = s->h_descs[f0].rows;
+        const int64_t tl = t0 + (int64_t)(rows - 1) * dt;
+        const int64_t wf = P.segq[f0].w_first;
+        const uint32_t nw = P.segq[f0].n_wins;
+        bool ok = dt > 0 && nw > 0 && win_ordinal(t0, interval, offset) == wf &&
+                  win_ordinal(tl, interval, offset) == wf + (int64_t)nw - 1 &&
+                  wf >= P.W0 && wf + (int64_t)nw <= P.W0 + (int64_t)P.n_gwins;
+        for (size_t j = a; ok && j < b; j++) {
+          const uint32_t si = gl[j];
+          ok = s->h_gor[si].t0 == t0 && s->h_gor[si].dt == dt &&
+               s->h_descs[si].rows == rows && P.segq[si].w_first == wf &&
+               P.segq[si].n_wins == nw && ser_ok[P.segq[si].series_idx];
+        }
+        fw[wv] = {-1, 0, 0, 0};
+        if (!ok) continue;
+        auto key = std::make_tuple(t0, dt, rows);
+        auto it = tabs.find(key);
+        if (it == tabs.end()) {
+          const uint32_t off = (uint32_t)bounds.size();
+          bounds.push_back(0);
+          for (uint32_t k = 0; k < nw; k++) {
+            /* rows with t < window end: ceil((we - t0) / dt), we > t0 */
+            const int64_t we = (wf + k + 1) * interval + offset;
+            const int64_t nb = (we - t0 + dt - 1) / dt;
+            bounds.push_back((uint32_t)std::min<int64_t>(nb, rows));
+          }
+          it = tabs.emplace(key, off).first;
+        }
+        fw[wv] = {(int32_t)nfold++, it->second, nw, (uint32_t)(wf - P.W0)};
+        for (size_t j = a; j < b; j++) folded[gl[j]] = 1;
+        P.fold_segs += b - a;
+      }
+      if (nfold) {
+        std::vector<uint32_t> sel;
+        for (size_t g = 0; g < P.sq.size(); g++) {
+          const auto &r = s->series_ranges[g];
+          for (uint32_t i = r.start; i < r.start + r.count; i++)
+            if (P.segq[i].n_wins && !folded[i]) {
+              sel.push_back((uint32_t)g);
+              break;
+            }
+        }
+        P.n_fold_waves = nfold;
+        P.n_p1_sel = (uint32_t)sel.size();
+        if (!sel.empty()) {
+          uint64_t want = (2048 + P.n_gwins - 1) / P.n_gwins;
+          uint64_t pc = (sel.size() + want - 1) / want;
+          pc = std::max<uint64_t>(pc, (sel.size() + P.gsplit - 1) / P.gsplit);
+          if (pc < 256) pc = 256;
+          if (pc > sel.size()) pc = sel.size();
+          P.fper_chunk = (uint32_t)pc;
+          P.fsplit = (uint32_t)((sel.size() + pc - 1) / pc); /* <= gsplit */
+        }
+        HIP_CHECK(hipMalloc(&P.d_fwaves, sizeof(FoldWave) * fw.size()));
+        HIP_CHECK(hipMemcpyAsync(P.d_fwaves, fw.data(),
+                                 sizeof(FoldWave) * fw.size(),
+                                 hipMemcpyHostToDevice, s->stream));
+        HIP_CHECK(hipMalloc(&P.d_fbounds, sizeof(uint32_t) * bounds.size()));
+        HIP_CHECK(hipMemcpyAsync(P.d_fbounds, bounds.data(),
+                                 sizeof(uint32_t) * bounds.size(),
+                                 hipMemcpyHostToDevice, s->stream));
+        HIP_CHECK(hipMalloc(&P.d_seg_folded, folded.size()));
+        HIP_CHECK(hipMemcpyAsync(P.d_seg_folded, folded.data(), folded.size(),
+                                 hipMemcpyHostToDevice, s->stream));
+        HIP_CHECK(hipMalloc(&P.d_p1_sel,
+                            sizeof(uint32_t) * (sel.empty() ? 1 : sel.size())));
+        if (!sel.empty())
+          HIP_CHECK(hipMemcpyAsync(P.d_p1_sel, sel.data(),
+                                   sizeof(uint32_t) * sel.size(),
+                                   hipMemcpyHostToDevice, s->stream));
+        /* zeroed once: a wave only ever writes the windows it covers, the
+         * rest must read as unused */
+        const size_t fbytes = sizeof(GAcc) * P.n_gwins * nfold;
+        HIP_CHECK(hipMalloc(&P.d_fold, fbytes));
+        HIP_CHECK(hipMemsetAsync(P.d_fold, 0, fbytes, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream)); /* sources are locals */
+      }
+    }
+    for (const SegQ &q : P.segq) P.scan_segs += q.n_wins ? 1 : 0;
     P.start = start_time;
     P.end = end_time;
     P.interval = interval;
@@ -5339,8 +5690,8 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     P.skip_hash = skip_hash;
     P.valid = true;
   }
-  const int slot = s->q_slot;
-  s->q_slot ^= 1;
+  const int slot = redo_slot >= 0 ? redo_slot : s->q_slot;
+  if (redo_slot < 0) s->q_slot ^= 1;
   SegQ *d_segq = P.d_segq;
   SeriesQ *d_sq = P.d_sq;
   Partial *d_part = P.d_part;
@@ -5402,6 +5753,17 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
   /* A/B escape hatch for profiling: route gorilla segments through the
    * generic grid kernel instead of k_scan_grid_gor */
   static const bool no_gork = getenv("GEMX_DISABLE_GORK") != nullptr;
+  /* wave fold is a launch-time decision on a shared plan */
+  const bool fold = group_all && !tagq && use_grid && !no_gork &&
+                    P.n_fold_waves > 0 && !P.fold_off;
+  s->fold_q[slot].folded = fold;
+  s->fold_q[slot].keep_empty = keep_empty;
+  s->fold_q[slot].cap = cap;
+  if (group_all && !tagq) {
+    s->last_fold_folded = fold ? P.fold_segs : 0;
+    s->last_fold_scanned = P.scan_segs;
+    s->last_fold_redo = redo_slot >= 0;
+  }
   struct FastLaunch {
     const uint32_t *list;
     uint32_t n;
@@ -5426,7 +5788,10 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     uint32_t blocks = std::min<uint32_t>((n + tpb - 1) / tpb, 65535);
     const uint32_t *lst = launches[li].list;
     if (launches[li].gridp == 2) {
-      if (P.d_subq && !P.clipped) { /* underfill split: lane per SUB */
+      /* underfill split: lane per SUB. Plans with the split carry no
+       * fold table unless GEMX_FOLD_UNDERFILLED asked for one; a folding
+       * launch keeps whole segments per lane (it needs the aligned wave) */
+      if (P.d_subq && !P.clipped && !fold) {
         uint32_t nsubs = (uint32_t)s->h_subs.size();
         uint32_t stpb = (nsubs < 64 * 1024) ? 64 : 256;
         uint32_t sblocks = std::min<uint32_t>((nsubs + stpb - 1) / stpb, 65535);
@@ -5443,10 +5808,18 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                              P.d_subpart);
         continue;
       }
-      hipLaunchKernelGGL(k_scan_grid_gor, dim3(blocks), dim3(tpb), 0,
-                         s->stream, s->d_arena, s->arena_words, s->d_gor,
-                         s->d_descs, d_segq, lst, n, d_part, interval,
-                         offset, d_err);
+      if (fold)
+        hipLaunchKernelGGL(k_scan_grid_gor<true>, dim3(blocks), dim3(tpb), 0,
+                           s->stream, s->d_arena, s->arena_words, s->d_gor,
+                           s->d_descs, d_segq, lst, n, d_part, interval,
+                           offset, d_err, P.d_fwaves, P.d_fbounds,
+                           (GAcc *)P.d_fold, P.n_fold_waves);
+      else
+        hipLaunchKernelGGL(k_scan_grid_gor<false>, dim3(blocks), dim3(tpb), 0,
+                           s->stream, s->d_arena, s->arena_words, s->d_gor,
+                           s->d_descs, d_segq, lst, n, d_part, interval,
+                           offset, d_err, (const FoldWave *)nullptr,
+                           (const uint32_t *)nullptr, (GAcc *)nullptr, 0u);
       continue;
     }
     if (launches[li].gridp == 3) { /* lane per raw segment, arena-fed */
@@ -5627,6 +6000,22 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                          0, s->stream, d_sq, (uint32_t)sq.size(), d_segq,
                          d_part, P.d_grows2[slot], P.W0, (uint32_t)P.n_gwins,
                          interval, offset, start_time, keep_empty, d_err);
+  } else if (!tagq && group_all && P.n_gwins > 0 && fold) {
+    /* folded waves already hold their per-window GAcc: p1 only covers the
+     * series that still own a non-folded segment (skipped when none) */
+    uint32_t b1 = (uint32_t)std::min<uint64_t>(P.n_gwins * P.fsplit, 65535);
+    uint32_t b2 = (uint32_t)std::min<uint64_t>(P.n_gwins, 65535);
+    if (P.n_p1_sel)
+      hipLaunchKernelGGL((k_group_p1<GEMX_TYPE_FLOAT, true>), dim3(b1),
+                         dim3(256), 0, s->stream, d_sq, P.n_p1_sel, d_segq,
+                         d_part, (GAcc *)P.d_gtmp, P.W0, (uint32_t)P.n_gwins,
+                         P.fsplit, P.fper_chunk, P.d_p1_sel, P.d_seg_folded);
+    hipLaunchKernelGGL((k_group_p2<GEMX_TYPE_FLOAT>), dim3(b2), dim3(256), 0,
+                       s->stream, (const GAcc *)P.d_gtmp,
+                       P.n_p1_sel ? P.fsplit : 0u, P.d_grows2[slot], P.W0,
+                       (uint32_t)P.n_gwins, interval, offset, start_time,
+                       keep_empty, d_err, (const GAcc *)P.d_fold,
+                       P.n_fold_waves);
   } else if (!tagq && group_all && P.n_gwins > 0) {
     uint32_t b1 = (uint32_t)std::min<uint64_t>(P.n_gwins * P.gsplit, 65535);
     uint32_t b2 = (uint32_t)std::min<uint64_t>(P.n_gwins, 65535);
@@ -5704,6 +6093,18 @@ static int scan_deliver(gemx_shard *s, int slot, uint64_t fetch_rows,
                                            : "segment decode failed on device");
     return herr.code;
   }
+  if (s->fold_q[slot].folded && herr.fold_nan != 0) {
+    /* a folded window started on NaN: its min/max depend on the merge
+     * tree's shape, so this plan stops folding and the query runs again
+     * on the per-segment path before anything is returned */
+    QueryPlan &P = s->plan;
+    s->fold_q[slot].folded = false;
+    P.fold_off = true;
+    return scan_impl(s, P.start, P.end, P.interval, P.offset, 1, 0, 0, 0,
+                     out_host, s->fold_q[slot].cap, n_out, stats, nullptr,
+                     nullptr, 0, nullptr, nullptr, s->fold_q[slot].keep_empty,
+                     slot);
+  }
 
   /* in-place gap compaction (count == -1). The merge kernels counted the
    * gap rows on device, so the common all-populated case skips the host
@@ -5736,6 +6137,15 @@ static int scan_deliver(gemx_shard *s, int slot, uint64_t fetch_rows,
     stats->n_rows = n;
     stats->h2d_ms = sync_ms + comp_ms; /* repurposed: host sync+compact ms */
   }
+  return GEMX_OK;
+}
+
+extern "C" int gemx_fold_stats(gemx_shard *s, uint64_t *folded_segments,
+                               uint64_t *scanned_segments, uint32_t *redone) {
+  if (!s) return GEMX_E_INVALID;
+  if (folded_segments) *folded_segments = s->last_fold_folded;
+  if (scanned_segments) *scanned_segments = s->last_fold_scanned;
+  if (redone) *redone = s->last_fold_redo;
   return GEMX_OK;
 }
 

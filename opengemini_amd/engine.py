@@ -133,6 +133,11 @@ def _load():
     lib.gemx_scan_agg.argtypes = scan_sig
     lib.gemx_scan_agg_grouped.restype = C.c_int
     lib.gemx_scan_agg_grouped.argtypes = scan_sig
+    lib.gemx_fold_stats.restype = C.c_int
+    lib.gemx_fold_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint32),
+    ]
     lib.gemx_scan_agg_ex.restype = C.c_int
     lib.gemx_scan_agg_ex.argtypes = [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
@@ -496,6 +501,18 @@ class Shard:
         )
         return out[: n.value], stats
 
+
+    def fold_stats(self):
+        """Wave-fold coverage of the last grouped query on this shard:
+        dict(folded=<segments reduced in the scan kernel>,
+        scanned=<in-range segments>, redone=<True when a NaN window forced
+        an unfolded re-run>)."""
+        f = C.c_uint64(0)
+        n = C.c_uint64(0)
+        r = C.c_uint32(0)
+        _check(self._lib.gemx_fold_stats(self._h, C.byref(f), C.byref(n),
+                                         C.byref(r)), self._lib)
+        return dict(folded=f.value, scanned=n.value, redone=bool(r.value))
 
     def scan_agg_begin(self, start_time, end_time, interval, offset=0,
                        group_all=False, out_cap=None, buf_id=0):
