@@ -35,6 +35,7 @@ extern "C" {
  * protoparser/influx/parser.go:1363-1370) */
 #define GEMX_TYPE_INT 1
 #define GEMX_TYPE_FLOAT 3
+#define GEMX_TYPE_BOOL 5
 
 /* error codes */
 #define GEMX_OK 0
@@ -71,7 +72,12 @@ typedef union {
 
 /* One (sid, window) aggregate row. Semantics documented field-by-field in
  * oracle/oracle.h (orc_agg_row); layouts are kept identical so parity tests
- * can compare buffers directly. */
+ * can compare buffers directly.
+ * Boolean columns (GEMX_TYPE_BOOL) carry minv/maxv/firstv/lastv as .i in
+ * {0,1} (false < true); they have no sum: sum.i = 0 and sum_isnil = 1 on
+ * every row. All other fields, sum_time included, are what the int64
+ * column holding the same rows as 0/1 reports (the boolean reducers are
+ * instances of the integer templates, engine/series_agg_func.gen.go). */
 typedef struct {
   uint64_t sid;
   int64_t win_start;
@@ -168,11 +174,21 @@ int gemx_scan_agg_grouped(gemx_shard *, int64_t start_time, int64_t end_time,
 int gemx_fold_stats(gemx_shard *, uint64_t *folded_segments,
                     uint64_t *scanned_segments, uint32_t *redone);
 
+/* Routing of the shard's last aggregate scan on a boolean column: how many
+ * in-range segments the bit-parallel kernel (k_scan_bool_grid: full blocks
+ * on a const-delta time grid, interval > 0, no own-column predicate, not
+ * clipped by the query range) reduced, and how many went to any other
+ * kernel. Either out pointer may be NULL. Zeros on non-boolean shards. */
+int gemx_bool_stats(gemx_shard *, uint64_t *bitpar_segments,
+                    uint64_t *other_segments);
+
 /* value-predicate pushdown (config #3): lib/binaryfilterfunc compare
  * kernels (eval_generator.gen.go:31+) with FilterByField semantics
  * (immutable/location.go:309) — rows failing the predicate (and nil rows)
  * are removed before aggregation. filter_op: 0 none, 1 >, 2 >=, 3 <, 4 <=,
- * 5 ==, 6 != against filter_f (float cols) / filter_i (int cols). */
+ * 5 ==, 6 != against filter_f (float cols) / filter_i (int cols).
+ * Boolean columns take only == and != against filter_i in {0,1}
+ * (GetBooleanEQ/NEQConditionBitMap); anything else is GEMX_E_INVALID. */
 #define GEMX_FILTER_NONE 0
 #define GEMX_FILTER_GT 1
 #define GEMX_FILTER_GE 2
@@ -413,7 +429,8 @@ int gemx_prom_over_time(gemx_shard *, int64_t start_time, int64_t end_time,
 
 /* Rows must be grouped by sid with times ascending within each sid (the
  * order ChunkMeta/WriteRecord requires). values holds one element per row
- * (float64 for GEMX_TYPE_FLOAT, int64 for GEMX_TYPE_INT); rows whose
+ * (float64 for GEMX_TYPE_FLOAT, int64 for GEMX_TYPE_INT, one uint8_t in
+ * {0,1} for GEMX_TYPE_BOOL — any other byte is GEMX_E_INVALID); rows whose
  * valid[i]==0 are nil (valid==NULL ⇒ all rows valid). Segments are cut at
  * sid changes and every seg_rows rows (≤1000 in the reference,
  * config.maxRowsPerSegment). Writes the blob and one gemx_seg_desc per
@@ -481,7 +498,8 @@ int gemx_shard_set_preagg(gemx_shard *, const gemx_agg_row *rows, uint64_t n);
  * row time (the multiCall time-column semantics of the aggregate cursor,
  * see oracle/oracle.h), nil aggregates written as nil rows.
  * GEMX_OP_COUNT always writes a GEMX_TYPE_INT column; other ops keep the
- * source column type. The output attaches with gemx_shard_attach and is
+ * source column type. Boolean shards have no sum: GEMX_OP_SUM on one is
+ * GEMX_E_INVALID. The output attaches with gemx_shard_attach and is
  * readable by the reference's segment readers. */
 int gemx_downsample_write(gemx_shard *, int64_t start_time, int64_t end_time,
                           int64_t interval, int64_t offset, int op,
@@ -525,8 +543,10 @@ typedef struct {
  * aggregate_cursor.go: multi-call queries (n_ops > 1) use the window's
  * first row time (deriveIntervalIndex :371-374); single-call queries
  * use the call's own time (series_agg_reducer.gen.go:244,269).
- * GEMX_OP_COUNT columns are int64; other ops keep col_type. Returns
- * GEMX_OK or GEMX_E_INVALID. */
+ * GEMX_OP_COUNT columns are int64; other ops keep col_type. With
+ * GEMX_TYPE_BOOL the value columns pack ONE byte per value (as
+ * record.ColVal holds booleans) and GEMX_OP_SUM is GEMX_E_INVALID.
+ * Returns GEMX_OK or GEMX_E_INVALID. */
 int gemx_rec_from_rows(const gemx_agg_row *rows, uint64_t n_rows,
                        const int *ops, int n_ops, int col_type,
                        void *const *val_bufs, uint8_t *const *bitmaps,

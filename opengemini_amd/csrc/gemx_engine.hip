@@ -1941,6 +1941,171 @@ __global__ void __launch_bounds__(256) k_scan_grid_s8b(
   }
 }
 
+/* ---------------- lane-per-segment bit-parallel boolean kernel ----------
+ *
+ * A full boolean block is a bare bit string (lib/encoding/bool.go:40-61):
+ * [tag33][rows u32be][1<<4][count u32be][ceil(count/8) bytes], value k at
+ * bit 7-(k&7) of byte k>>3 — read as big-endian 64-bit words, row k is bit
+ * 63-(k&63) of word k>>6. On a const-delta time grid each window is a
+ * contiguous row range [r0, r1) found with the same closed-form arithmetic
+ * as k_scan_grid_s8b (one 64-bit division per window), and its aggregates
+ * need no per-row loop (booleanCountReduce / booleanMin/Max/First/Last in
+ * engine/series_agg_func.gen.go, false < true, first occurrence wins):
+ *   count = r1-r0, first = bit r0, last = bit r1-1,
+ *   min   = 0 at the first zero row (clz of the inverted masked word) else
+ *           1 at r0,  max = 1 at the first one row else 0 at r0.
+ * A window wider than a word scans words, not rows. Only the current and
+ * the next word are live (loaded as the window cursor advances): no
+ * indexed private array, no scratch. Partials carry integer 0/1 payloads
+ * so the merge/group/tag stages run their GEMX_TYPE_INT instantiations
+ * unchanged; the popcount goes into the sum slot (what the int twin holds)
+ * and the host-visible rows get their sum blanked by k_blank_sum. The
+ * one-row form [tag19][value byte] is a one-bit string. Routing guarantee
+ * (classify_segment): header validated on the host, payload at least
+ * ceil(rows/8) bytes. */
+__device__ __forceinline__ uint64_t d_bool_word(const uint8_t *bits, int nbytes,
+                                                int w) {
+  const int off = w * 8;
+  if (off + 8 <= nbytes) return d_u64be(bits + off);
+  /* tail word: never read past the payload */
+  uint64_t v = 0;
+  for (int k = 0; k < 8; k++)
+    if (off + k < nbytes) v |= (uint64_t)bits[off + k] << (56 - 8 * k);
+  return v;
+}
+
+__global__ void __launch_bounds__(256) k_scan_bool_grid(
+    const uint8_t *__restrict__ blob, const gemx_seg_desc *__restrict__ descs,
+    const SegQ *__restrict__ segq, const uint32_t *__restrict__ seg_ids,
+    uint32_t nseg_ids, Partial *__restrict__ partials, int64_t interval,
+    int64_t offset, DevErr *err) {
+  uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  for (uint32_t li = gid; li < nseg_ids; li += gridDim.x * blockDim.x) {
+    uint32_t si = seg_ids[li];
+    const gemx_seg_desc d = descs[si];
+    const SegQ sq = segq[si];
+    if (sq.n_wins == 0) continue;
+
+    /* const-delta time (routing guarantee; timestamp.go:190) */
+    int64_t t0c, dtc;
+    {
+      const uint8_t *tseg = blob + d.time_offset;
+      if (tseg[0] == 18) {
+        t0c = (int64_t)d_u64le(tseg + 1);
+        dtc = 0;
+      } else {
+        TimeIter ti;
+        if (ti.init(tseg + 5, d.time_size - 5) || ti.kind != 1 ||
+            ti.left < (int64_t)d.rows) {
+          set_err(err, GEMX_E_DECODE);
+          return;
+        }
+        t0c = ti.cur;
+        dtc = ti.delta;
+      }
+    }
+    const int rows = (int)d.rows;
+    const uint8_t *seg = blob + d.data_offset;
+    const uint8_t *bits = seg + 10;
+    int nbytes = (rows + 7) >> 3;
+    /* current word index and the (current, next) word pair */
+    int cwi = 0;
+    uint64_t w0, w1;
+    if (seg[0] == 19) { /* one-row form: a one-bit string */
+      if (rows != 1 || d.data_size != 2) {
+        set_err(err, GEMX_E_DECODE);
+        return;
+      }
+      nbytes = 0;
+      w0 = (uint64_t)(seg[1] & 1) << 63;
+      w1 = 0;
+    } else {
+      if (seg[0] != 33 || d.data_size < 10 + (uint32_t)nbytes ||
+          (seg[5] >> 4) != 1 || d_u32be(seg + 6) != (uint32_t)rows) {
+        set_err(err, GEMX_E_DECODE);
+        return;
+      }
+      w0 = d_bool_word(bits, nbytes, 0);
+      w1 = d_bool_word(bits, nbytes, 1);
+    }
+
+    Partial *base = partials + sq.partial_base;
+    for (uint32_t k = 0; k < sq.n_wins; k++) base[k].has_rows = 0;
+
+    int i = 0;
+    while (i < rows) {
+      int64_t t_i = t0c + (int64_t)i * dtc;
+      int64_t ord = win_ordinal(t_i, interval, offset);
+      if (ord < sq.w_first || ord >= sq.w_first + (int64_t)sq.n_wins) {
+        set_err(err, GEMX_E_INVALID);
+        return;
+      }
+      int64_t we = ord * interval + offset + interval;
+      int gend;
+      if (dtc == 0) {
+        gend = rows;
+      } else {
+        int64_t n_in = (we - 1 - t_i) / dtc + 1;
+        gend = (n_in >= (int64_t)(rows - i)) ? rows : i + (int)n_in;
+      }
+      /* rows [i, gend): words wa..wb, masked at both ends */
+      const int wa = i >> 6, wb = (gend - 1) >> 6;
+      int first_one = -1, first_zero = -1;
+      int64_t ones = 0;
+      uint64_t firstb = 0, lastb = 0;
+      for (int w = wa; w <= wb; w++) {
+        while (w > cwi + 1) { /* slide the pair; one load per new word */
+          cwi++;
+          w0 = w1;
+          w1 = d_bool_word(bits, nbytes, cwi + 1);
+        }
+        const uint64_t word = (w == cwi) ? w0 : w1;
+        const int lo = (w == wa) ? (i & 63) : 0;            /* first bit in */
+        const int hi = (w == wb) ? ((gend - 1) & 63) + 1 : 64; /* one past */
+        uint64_t mask = ~0ULL >> lo;
+        if (hi < 64) mask &= ~(~0ULL >> hi);
+        const uint64_t one_m = word & mask, zero_m = ~word & mask;
+        ones += __builtin_popcountll(one_m);
+        if (first_one < 0 && one_m) first_one = w * 64 + __builtin_clzll(one_m);
+        if (first_zero < 0 && zero_m)
+          first_zero = w * 64 + __builtin_clzll(zero_m);
+        if (w == wa) firstb = (word >> (63 - lo)) & 1;
+        if (w == wb) lastb = (word >> (64 - hi)) & 1;
+      }
+      Partial tmp;
+      tmp.v[0].i = gend - i;
+      tmp.v[1].i = ones;
+      tmp.v[2].i = first_zero >= 0 ? 0 : 1;
+      tmp.v[3].i = first_one >= 0 ? 1 : 0;
+      tmp.v[4].i = (int64_t)firstb;
+      tmp.v[5].i = (int64_t)lastb;
+      tmp.t[0] = t_i;
+      tmp.t[1] = t_i; /* no nils: valueIndex == row index */
+      tmp.t[2] = t0c + (int64_t)(first_zero >= 0 ? first_zero : i) * dtc;
+      tmp.t[3] = t0c + (int64_t)(first_one >= 0 ? first_one : i) * dtc;
+      tmp.t[4] = t_i;
+      tmp.t[5] = t0c + (int64_t)(gend - 1) * dtc;
+      tmp.first_row_time = t_i;
+      tmp.nilmask = 0;
+      tmp.has_rows = 1;
+      base[ord - sq.w_first] = tmp;
+      i = gend;
+    }
+  }
+}
+
+/* boolean columns have no sum aggregate: blank it on the emitted rows (the
+ * merge stages ran their integer instantiations on 0/1 partials; sum_time
+ * stays what the integer path reports) */
+__global__ void __launch_bounds__(256) k_blank_sum(gemx_agg_row *__restrict__ rows,
+                                                   uint64_t n) {
+  uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  for (; i < n; i += gridDim.x * (uint64_t)blockDim.x) {
+    rows[i].sum.i = 0;
+    rows[i].sum_isnil = 1;
+  }
+}
+
 /* ---------------- lane-per-segment RAW float kernel ----------------
  *
  * Raw (uncompressed) float blocks — the reference's fallback when gorilla
@@ -2111,6 +2276,19 @@ __global__ void __launch_bounds__(256) k_scan_raw_lane(
 __device__ int64_t d_snappy_decode(const uint8_t *src, int64_t len,
                                    uint8_t *dst, int64_t cap);
 
+/* boolean dense block (lib/encoding/bool.go:63-96): [1<<4][count u32be]
+ * [bits, MSB-first] unpacked to int64 0/1. Returns the count, -1 when the
+ * header is wrong or the payload is shorter than ceil(count/8) bytes. */
+__device__ int d_bool_decode(const uint8_t *enc, int64_t enc_len,
+                             int64_t *vbuf) {
+  if (enc_len < 5 || (enc[0] >> 4) != 1) return -1;
+  const uint32_t cnt = d_u32be(enc + 1);
+  if (cnt > 4096 || enc_len < 5 + (int64_t)((cnt + 7) >> 3)) return -1;
+  for (uint32_t k = 0; k < cnt; k++)
+    vbuf[k] = (enc[5 + (k >> 3)] >> (7 - (k & 7))) & 1;
+  return (int)cnt;
+}
+
 template <int FCOLTYPE>
 __global__ void __launch_bounds__(256) k_eval_filter(
     const uint8_t *__restrict__ blob, const gemx_seg_desc *__restrict__ descs,
@@ -2138,10 +2316,17 @@ __global__ void __launch_bounds__(256) k_eval_filter(
     if (h.one_value) {
       nilcount = h.nilcount;
       dense = 1 - nilcount;
-      if (dense) memcpy(&vbuf[0], h.enc, 8);
+      if (dense) {
+        if (FCOLTYPE == GEMX_TYPE_BOOL) vbuf[0] = h.enc[0] & 1; /* one byte */
+        else memcpy(&vbuf[0], h.enc, 8);
+      }
     } else if (h.enc_len == 0) {
       nilcount = h.nilcount;
       dense = 0;
+    } else if (FCOLTYPE == GEMX_TYPE_BOOL) {
+      dense = d_bool_decode(h.enc, h.enc_len, vbuf);
+      if (dense < 0) { set_err(err, GEMX_E_DECODE); return; }
+      nilcount = h.bitmap ? h.nilcount : 0;
     } else if (FCOLTYPE == GEMX_TYPE_FLOAT) {
       int tag = h.enc[0] >> 4;
       if (tag == 2) {
@@ -2339,10 +2524,19 @@ __global__ void __launch_bounds__(256) k_scan_general(
     if (h.one_value) {
       nilcount = h.nilcount;
       dense = 1 - nilcount;
-      if (dense) memcpy(&vbuf[0], h.enc, 8);
+      if (dense) {
+        if (COLTYPE == GEMX_TYPE_BOOL) vbuf[0] = h.enc[0] & 1; /* one byte */
+        else memcpy(&vbuf[0], h.enc, 8);
+      }
     } else if (h.enc_len == 0) { /* empty block */
       nilcount = h.nilcount;
       dense = 0;
+    } else if (COLTYPE == GEMX_TYPE_BOOL) {
+      /* bit-packed booleans unpack to int64 0/1; the integer reducer below
+       * then applies unchanged (the boolean reducers are the same templates) */
+      dense = d_bool_decode(h.enc, h.enc_len, vbuf);
+      if (dense < 0) { set_err(err, GEMX_E_DECODE); return; }
+      nilcount = h.bitmap ? h.nilcount : 0;
     } else if (COLTYPE == GEMX_TYPE_FLOAT) {
       int tag = h.enc[0] >> 4;
       if (tag == 2) { /* snappy floats (compress.go:81-84,149) */
@@ -4367,6 +4561,8 @@ struct gemx_shard {
   } fold_q[2]; /* per slot: what scan_deliver needs to redo unfolded */
   uint64_t last_fold_folded = 0, last_fold_scanned = 0;
   uint32_t last_fold_redo = 0;
+  /* boolean shards: routing of the last aggregate scan (gemx_bool_stats) */
+  uint64_t last_bool_bitpar = 0, last_bool_other = 0;
   uint64_t total_rows_scanned; /* Σ rows */
   uint64_t total_compressed_bytes = 0; /* Σ data+time segment bytes (cached:
       summing 1M descriptors per query in scan_deliver cost ~1 ms/step on
@@ -4479,6 +4675,57 @@ static int h_uvarint(const uint8_t *p, int64_t len, uint64_t *out) {
   return -1;
 }
 
+/* Boolean data segment (lib/encoding/bool.go, encoding.go:36-62,
+ * column_builder.go:302-349): validates the whole header and that the bit
+ * payload is as long as its count says, so no kernel can read past a
+ * segment. *dense_full = a full block or a valid one-row block (the forms
+ * k_scan_bool_grid takes). Layouts:
+ *   full    [33][rows u32be][1<<4][count u32be][ceil(count/8) bytes]
+ *   bitmap  [5][bmlen u32be][bitmap][bm_off u32be][nilcount u32be]
+ *           [1<<4][count u32be][bits]
+ *   one row [19][value byte], or [19] alone for a nil row
+ *   empty   [43][rows u32be] */
+static int classify_bool_data(const uint8_t *ds, const gemx_seg_desc &d,
+                              bool *dense_full) {
+  *dense_full = false;
+  const uint8_t dt = ds[0];
+  const uint64_t size = d.data_size;
+  if (dt == 19) {
+    if (d.rows != 1 || size > 2) return GEMX_E_INVALID;
+    if (size == 2 && ds[1] > 1) return GEMX_E_INVALID;
+    *dense_full = (size == 2);
+    return 0;
+  }
+  if (dt == 43) {
+    if (size < 5 || h_u32be(ds + 1) != d.rows) return GEMX_E_INVALID;
+    return 0;
+  }
+  if (dt == 33) {
+    if (size < 10 || h_u32be(ds + 1) != d.rows) return GEMX_E_INVALID;
+    if ((ds[5] >> 4) != 1) return GEMX_E_INVALID; /* boolCompressedBitpack */
+    const uint64_t count = h_u32be(ds + 6);
+    if (count != d.rows) return GEMX_E_INVALID;
+    if (size < 10 + (count + 7) / 8) return GEMX_E_INVALID;
+    *dense_full = true;
+    return 0;
+  }
+  if (dt == GEMX_TYPE_BOOL) {
+    if (size < 13) return GEMX_E_INVALID;
+    const uint64_t bmlen = h_u32be(ds + 1);
+    if (size < 13 + bmlen + 5) return GEMX_E_INVALID;
+    const uint64_t bm_off = h_u32be(ds + 5 + bmlen);
+    const uint64_t nil = h_u32be(ds + 9 + bmlen);
+    const uint8_t *enc = ds + 13 + bmlen;
+    if ((enc[0] >> 4) != 1) return GEMX_E_INVALID;
+    const uint64_t count = h_u32be(enc + 1);
+    if (nil > d.rows || count != d.rows - nil) return GEMX_E_INVALID;
+    if (bm_off + d.rows > bmlen * 8) return GEMX_E_INVALID;
+    if (size < 13 + bmlen + 5 + (count + 7) / 8) return GEMX_E_INVALID;
+    return 0;
+  }
+  return GEMX_E_INVALID;
+}
+
 /* attach-time classification: peek headers in HOST memory.
  * *grid = const-delta timestamps with non-negative delta — segments the
  * leaner GRIDP=1 instantiation of k_scan_fast can take. */
@@ -4510,6 +4757,16 @@ static int classify_segment(const uint8_t *blob, const gemx_seg_desc &d, int col
     }
   } else
     return GEMX_E_INVALID;
+  if (col_type == GEMX_TYPE_BOOL) {
+    if (ts[0] == 18 && d.time_size < 9) return GEMX_E_INVALID;
+    int rc = classify_bool_data(ds, d, fast);
+    /* bit-parallel eligible: full (or one-row) block on a const-delta
+     * grid. Boolean shards have no other fast kernel, so the segment rides
+     * the s8b launch slot, which runs k_scan_bool_grid for them. */
+    *fast = *fast && *grid;
+    *s8b = *fast;
+    return rc;
+  }
   /* data */
   if (dt > 16 && dt < 21) {
     if (d.data_size <= 1) *fast = false; /* one-value null row: general */
@@ -5030,8 +5287,9 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
     seterr("no HIP device: the MI355X engine has no CPU fallback");
     return GEMX_E_NOGPU;
   }
-  if (col_type != GEMX_TYPE_FLOAT && col_type != GEMX_TYPE_INT) {
-    seterr("col_type must be GEMX_TYPE_FLOAT or GEMX_TYPE_INT");
+  if (col_type != GEMX_TYPE_FLOAT && col_type != GEMX_TYPE_INT &&
+      col_type != GEMX_TYPE_BOOL) {
+    seterr("col_type must be GEMX_TYPE_FLOAT, GEMX_TYPE_INT or GEMX_TYPE_BOOL");
     return GEMX_E_INVALID;
   }
   HIP_CHECK(hipSetDevice(device));
@@ -5298,6 +5556,20 @@ static int scan_deliver(gemx_shard *s, int slot, uint64_t fetch_rows,
                         gemx_agg_row *out_host, uint64_t *n_out,
                         gemx_query_stats *stats);
 
+/* boolean predicates: only == and != against a boolean operand exist
+ * (lib/binaryfilterfunc GetBooleanEQ/NEQConditionBitMap) */
+static int bool_filter_check(int filter_op, int64_t filter_i) {
+  if (filter_op != GEMX_FILTER_EQ && filter_op != GEMX_FILTER_NEQ) {
+    seterr("boolean columns compare with == and != only");
+    return GEMX_E_INVALID;
+  }
+  if (filter_i != 0 && filter_i != 1) {
+    seterr("boolean predicate operand must be 0 or 1");
+    return GEMX_E_INVALID;
+  }
+  return GEMX_OK;
+}
+
 static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                      int64_t interval, int64_t offset, int group_all,
                      int filter_op, double filter_f, int64_t filter_i,
@@ -5322,6 +5594,9 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     seterr("async queries in flight: call gemx_scan_agg_finish first");
     return GEMX_E_INVALID;
   }
+  const bool is_bool = (s->col_type == GEMX_TYPE_BOOL);
+  if (is_bool && filter_op != 0 && bool_filter_check(filter_op, filter_i))
+    return GEMX_E_INVALID;
   HIP_CHECK(hipSetDevice(s->device));
   const uint64_t nsegs = s->nsegs;
   const uint64_t scratch_per_lane =
@@ -5773,11 +6048,23 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
   if (use_grid) {
     if (gor_n) launches[n_launches++] = {gor_list, gor_n, no_gork ? 1 : 2};
     if (raw_n) launches[n_launches++] = {raw_list, raw_n, raw_ok ? 3 : 1};
-    if (s8b_n) launches[n_launches++] = {s8b_list, s8b_n, no_gork ? 1 : 4};
+    if (s8b_n)
+      launches[n_launches++] = {s8b_list, s8b_n,
+                                (no_gork && !is_bool) ? 1 : 4};
     if (grid_n) launches[n_launches++] = {grid_list, grid_n, 1};
     if (strm_n) launches[n_launches++] = {strm_list, strm_n, 0};
-  } else if (fast_n) {
+  } else if (fast_n && !is_bool) {
     launches[n_launches++] = {fast_list, fast_n, 0};
+  }
+  /* boolean shards: every fast segment is bit-parallel eligible and sits
+   * in the s8b slot (classify_segment). k_scan_bool_grid needs an
+   * interval and no predicate on this column; otherwise the same list
+   * goes through the general kernel. */
+  const uint32_t *bool_gen_list = fast_list;
+  const uint32_t bool_gen_n = (is_bool && !use_grid) ? fast_n : 0;
+  if (is_bool) {
+    s->last_bool_bitpar = use_grid ? s8b_n : 0;
+    s->last_bool_other = P.scan_segs - s->last_bool_bitpar;
   }
   for (int li = 0; li < n_launches; li++) {
     uint32_t n = launches[li].n;
@@ -5828,6 +6115,12 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                          lst, n, d_part, interval, offset, d_err);
       continue;
     }
+    if (launches[li].gridp == 4 && is_bool) { /* lane per boolean bit string */
+      hipLaunchKernelGGL(k_scan_bool_grid, dim3(blocks), dim3(tpb), 0,
+                         s->stream, s->d_blob, s->d_descs, d_segq, lst, n,
+                         d_part, interval, offset, d_err);
+      continue;
+    }
     if (launches[li].gridp == 4) { /* lane per simple8b int segment */
       hipLaunchKernelGGL(k_scan_grid_s8b, dim3(blocks), dim3(tpb), 0,
                          s->stream, s->d_blob, s->d_descs, d_segq, lst, n,
@@ -5856,7 +6149,34 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     }
 #undef GEMX_LAUNCH_FAST
   }
-  if (gen_n > 0) {
+  if (is_bool) {
+    /* the bit-parallel list runs through the general kernel too when the
+     * query has no interval or filters this column: size the lane scratch
+     * for the larger of the two lists (hipFree waits for queued work) */
+    const uint32_t need =
+        std::min<uint32_t>(std::max(gen_n, bool_gen_n), 16384);
+    if (d_scratch && gen_lanes < need) {
+      HIP_CHECK(hipFree(P.d_scratch));
+      P.d_scratch = d_scratch = nullptr;
+    }
+    if (!d_scratch && need) {
+      P.gen_lanes = need;
+      HIP_CHECK(hipMalloc(&P.d_scratch, scratch_per_lane * P.gen_lanes));
+      d_scratch = P.d_scratch;
+      gen_lanes = P.gen_lanes;
+    }
+    const uint32_t blocks = (gen_lanes + TPB - 1) / TPB;
+    const uint32_t *lists[2] = {gen_list, bool_gen_list};
+    const uint32_t ns[2] = {gen_n, bool_gen_n};
+    for (int k = 0; k < 2; k++)
+      if (ns[k])
+        hipLaunchKernelGGL((k_scan_general<GEMX_TYPE_BOOL>), dim3(blocks),
+                           dim3(TPB), 0, s->stream, s->d_blob, s->d_descs,
+                           d_segq, lists[k], ns[k], d_part, interval, offset,
+                           start_time, end_time, filter_op, filter_f, filter_i,
+                           d_scratch, scratch_per_lane, gen_lanes, xbm, xbase,
+                           d_err);
+  } else if (gen_n > 0) {
     if (!d_scratch) {
       /* clipping can route fast segments here on shards that had none */
       P.gen_lanes = (uint32_t)std::min<uint32_t>(gen_n, 16384);
@@ -6039,6 +6359,19 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                          offset, start_time, keep_empty, d_err);
     }
   }
+  if (is_bool) {
+    /* no sum aggregate on boolean columns: blank it on the rows this
+     * query emits (gap rows included; they are dropped on delivery) */
+    gemx_agg_row *er =
+        tagq ? s->tag_plan.d_rows : (group_all ? P.d_grows2[slot] : d_rows);
+    const uint64_t en = tagq ? (uint64_t)s->tag_plan.n_groups * P.n_gwins
+                             : (group_all ? P.n_gwins : total_rows);
+    if (en) {
+      uint32_t bb = (uint32_t)std::min<uint64_t>((en + 255) / 256, 65535);
+      hipLaunchKernelGGL(k_blank_sum, dim3(bb), dim3(256), 0, s->stream, er,
+                         en);
+    }
+  }
   HIP_CHECK(hipEventRecord(ev2, s->stream));
 
   /* hand the row fetch to the copy stream so it can overlap the NEXT
@@ -6146,6 +6479,14 @@ extern "C" int gemx_fold_stats(gemx_shard *s, uint64_t *folded_segments,
   if (folded_segments) *folded_segments = s->last_fold_folded;
   if (scanned_segments) *scanned_segments = s->last_fold_scanned;
   if (redone) *redone = s->last_fold_redo;
+  return GEMX_OK;
+}
+
+extern "C" int gemx_bool_stats(gemx_shard *s, uint64_t *bitpar_segments,
+                               uint64_t *other_segments) {
+  if (!s) return GEMX_E_INVALID;
+  if (bitpar_segments) *bitpar_segments = s->last_bool_bitpar;
+  if (other_segments) *other_segments = s->last_bool_other;
   return GEMX_OK;
 }
 
@@ -6660,7 +7001,15 @@ static int xfield_eval_into(gemx_shard *vs, gemx_shard *fs, int filter_op,
                         (uint64_t)(4096 * 8 + 40960) * vs->xlanes));
   }
   uint32_t blocks = (vs->xlanes + 255) / 256;
-  if (fs->col_type == GEMX_TYPE_FLOAT)
+  if (fs->col_type == GEMX_TYPE_BOOL) {
+    int brc = bool_filter_check(filter_op, filter_i);
+    if (brc) return brc;
+    hipLaunchKernelGGL((k_eval_filter<GEMX_TYPE_BOOL>), dim3(blocks),
+                       dim3(256), 0, vs->stream, fs->d_blob, fs->d_descs,
+                       (uint32_t)fs->nsegs, vs->d_row_base, filter_op,
+                       filter_f, filter_i, bm, vs->d_xscratch,
+                       (uint64_t)(4096 * 8 + 40960), vs->xlanes, e);
+  } else if (fs->col_type == GEMX_TYPE_FLOAT)
     hipLaunchKernelGGL((k_eval_filter<GEMX_TYPE_FLOAT>), dim3(blocks),
                        dim3(256), 0, vs->stream, fs->d_blob, fs->d_descs,
                        (uint32_t)fs->nsegs, vs->d_row_base, filter_op,
@@ -7117,17 +7466,26 @@ extern "C" int gemx_rec_from_rows(const gemx_agg_row *rows, uint64_t n_rows,
     seterr("rec_from_rows: bad arguments");
     return GEMX_E_INVALID;
   }
-  if (col_type != GEMX_TYPE_FLOAT && col_type != GEMX_TYPE_INT) {
+  if (col_type != GEMX_TYPE_FLOAT && col_type != GEMX_TYPE_INT &&
+      col_type != GEMX_TYPE_BOOL) {
     seterr("rec_from_rows: bad col_type");
     return GEMX_E_INVALID;
   }
   const uint64_t bm_bytes = (n_rows + 7) / 8;
+  for (int k = 0; k < n_ops; k++) {
+    if (col_type == GEMX_TYPE_BOOL && ops[k] == GEMX_OP_SUM) {
+      seterr("rec_from_rows: boolean columns have no sum");
+      return GEMX_E_INVALID; /* before any output buffer is touched */
+    }
+  }
   for (int k = 0; k < n_ops; k++) {
     const int op = ops[k];
     if (op < GEMX_OP_COUNT || op > GEMX_OP_LAST) {
       seterr("rec_from_rows: bad op");
       return GEMX_E_INVALID;
     }
+    /* record.ColVal holds booleans one byte each; counts stay int64 */
+    const bool byte_vals = (col_type == GEMX_TYPE_BOOL && op != GEMX_OP_COUNT);
     uint8_t *bm = bitmaps[k];
     memset(bm, 0, bm_bytes);
     gemx_val *dst = (gemx_val *)val_bufs[k];
@@ -7163,7 +7521,10 @@ extern "C" int gemx_rec_from_rows(const gemx_agg_row *rows, uint64_t n_rows,
         break;
       }
       if (!isnil) {
-        dst[dense++] = v;
+        if (byte_vals)
+          ((uint8_t *)val_bufs[k])[dense++] = (uint8_t)(v.i != 0);
+        else
+          dst[dense++] = v;
         bm[r >> 3] |= (uint8_t)(1u << (r & 7));
       }
     }

@@ -16,6 +16,7 @@
  *   float codec      lib/compress/float.go:164-254 (same-value / gorilla /
  *                    compressedNull; snappy and RLE branches replaced by
  *                    compressedNull raw, always valid per float.go:139 case 0)
+ *   bool block codec lib/encoding/bool.go:40-61 (bit-pack, MSB-first)
  *   gorilla          lib/util/lifted/influxdb/tsdb/engine/tsm1/
  *                    batch_float.go:17-254 (XOR-prev, 5b leading/6b
  *                    meaningful windows, UVNAN terminator)
@@ -168,8 +169,10 @@ static const uint64_t W_S8B_MAX = (1ULL << 60) - 1;
 static bool w_s8b_can_pack(const uint64_t *v, int64_t remn, int cnt, int bits) {
   if (remn < cnt) return false;
   if (bits == 0) {
-    for (int i = 0; i < cnt; i++)
-      if (v[i] != 0) return false;
+    /* selectors 0,1 encode runs of the VALUE 1, and the reference only
+     * takes them when every remaining value is 1 (encoding.go:454-462) */
+    for (int64_t i = 0; i < remn; i++)
+      if (v[i] != 1) return false;
     return true;
   }
   uint64_t maxv = (bits == 64) ? ~0ULL : ((1ULL << bits) - 1);
@@ -424,15 +427,33 @@ static int64_t w_float_encode(const double *src, int64_t n, uint8_t *dst,
   return 1 + g;
 }
 
+/* boolean block codec (bool.go:40-61): [1<<4][count u32be] then the values
+ * bit-packed MSB-first (value k at bit 7-(k&7) of byte k>>3), pad bits 0.
+ * src holds one byte (0/1) per value. */
+static int64_t w_bool_encode(const uint8_t *src, int64_t n, uint8_t *dst,
+                             int64_t cap) {
+  const int64_t nbytes = (n + 7) / 8;
+  if (cap < 5 + nbytes) return -1;
+  dst[0] = 1 << 4; /* boolCompressedBitpack */
+  wput_u32be(dst + 1, (uint32_t)n);
+  memset(dst + 5, 0, (size_t)nbytes);
+  for (int64_t k = 0; k < n; k++)
+    if (src[k]) dst[5 + (k >> 3)] |= (uint8_t)(0x80u >> (k & 7));
+  return 5 + nbytes;
+}
+
 /* segment wrappers (column_builder.go:428-501; chunkdata_builder.go:91-95).
- * vals is the DENSE (valid-only) value array; bitmap is LSB-first validity
- * over rows (may be null when nil_count is 0 or rows). */
+ * vals is the DENSE (valid-only) value array (8 bytes per value; one byte
+ * per value for booleans, column_builder.go:302-349); bitmap is LSB-first
+ * validity over rows (may be null when nil_count is 0 or rows). */
 static int64_t w_data_segment(int col_type, const void *vals,
                               const uint8_t *bitmap, int rows, int nil_count,
                               uint8_t *dst, int64_t cap) {
   int64_t dense = rows - nil_count;
-  int64_t val_bytes = dense * 8;
-  if (col_type != GEMX_TYPE_INT && col_type != GEMX_TYPE_FLOAT) return -1;
+  int64_t val_bytes = dense * (col_type == GEMX_TYPE_BOOL ? 1 : 8);
+  if (col_type != GEMX_TYPE_INT && col_type != GEMX_TYPE_FLOAT &&
+      col_type != GEMX_TYPE_BOOL)
+    return -1;
   if (rows == 1 && val_bytes > 0) { /* one-row (column_builder.go:489-491) */
     if (cap < 1 + val_bytes) return -1;
     dst[0] = w_blk_one(col_type);
@@ -463,6 +484,8 @@ static int64_t w_data_segment(int col_type, const void *vals,
   int64_t enc =
       (col_type == GEMX_TYPE_FLOAT)
           ? w_float_encode((const double *)vals, dense, dst + p, cap - p)
+      : (col_type == GEMX_TYPE_BOOL)
+          ? w_bool_encode((const uint8_t *)vals, dense, dst + p, cap - p)
           : w_int_encode((const int64_t *)vals, dense, dst + p, cap - p);
   if (enc < 0) return -1;
   return p + enc;
@@ -515,11 +538,14 @@ extern "C" int gemx_encode_shard(int col_type, const uint64_t *sids,
     seterr("seg_rows must be 1..4096 (reference maxRowsPerSegment is 1000)");
     return GEMX_E_INVALID;
   }
-  if (col_type != GEMX_TYPE_INT && col_type != GEMX_TYPE_FLOAT) {
-    seterr("col_type must be GEMX_TYPE_FLOAT or GEMX_TYPE_INT");
+  if (col_type != GEMX_TYPE_INT && col_type != GEMX_TYPE_FLOAT &&
+      col_type != GEMX_TYPE_BOOL) {
+    seterr("col_type must be GEMX_TYPE_FLOAT, GEMX_TYPE_INT or GEMX_TYPE_BOOL");
     return GEMX_E_INVALID;
   }
-  std::vector<int64_t> dense((size_t)seg_rows); /* valid values (8B each) */
+  const bool is_bool = (col_type == GEMX_TYPE_BOOL);
+  std::vector<int64_t> dense((size_t)seg_rows); /* valid values (8B each;
+      booleans pack one byte each into the same storage) */
   std::vector<int64_t> seg_t((size_t)seg_rows);
   std::vector<uint8_t> bm(((size_t)seg_rows + 7) / 8);
   uint64_t pos = 0, nseg = 0, off = 0;
@@ -539,7 +565,15 @@ extern "C" int gemx_encode_shard(int col_type, const uint64_t *sids,
     memset(bm.data(), 0, bm.size());
     for (int r = 0; r < rows; r++) {
       int ok = valid ? (valid[pos + r] != 0) : 1;
-      if (ok) {
+      if (ok && is_bool) {
+        const uint8_t b = ((const uint8_t *)values)[pos + r];
+        if (b > 1) {
+          seterr("boolean values must be 0 or 1");
+          return GEMX_E_INVALID;
+        }
+        ((uint8_t *)dense.data())[dn++] = b;
+        bm[(size_t)r >> 3] |= (uint8_t)(1u << (r & 7));
+      } else if (ok) {
         memcpy(&dense[(size_t)dn], (const uint8_t *)values + (pos + r) * 8, 8);
         dn++;
         bm[(size_t)r >> 3] |= (uint8_t)(1u << (r & 7));
@@ -646,7 +680,10 @@ static int w_preagg_build(int col_type, const uint64_t *sids,
       for (int r = 0; r < rows; r++) {
         if (valid && !valid[pos + r]) continue;
         gemx_val v;
-        memcpy(&v, (const uint8_t *)values + (pos + r) * 8, 8);
+        if (col_type == GEMX_TYPE_BOOL) /* one byte per row, reduced as 0/1 */
+          v.i = ((const uint8_t *)values)[pos + r];
+        else
+          memcpy(&v, (const uint8_t *)values + (pos + r) * 8, 8);
         if (cnt == 0) {
           mn = mx = fv = v;
           mn_row = mx_row = fv_row = r;
@@ -760,6 +797,10 @@ static int w_preagg_build(int col_type, const uint64_t *sids,
     o.sum = a[1].v;
     o.sum_time = a[1].active ? a[1].time : a[1].niltime;
     o.sum_isnil = !a[1].active;
+    if (col_type == GEMX_TYPE_BOOL) { /* no sum aggregate (sum_time stays) */
+      o.sum.i = 0;
+      o.sum_isnil = 1;
+    }
     o.minv = a[2].v;
     o.min_time = a[2].active ? a[2].time : a[2].niltime;
     o.min_isnil = !a[2].active;
@@ -820,8 +861,13 @@ static int ds_write_impl(gemx_shard *s, int64_t start_time,
                          uint64_t descs_cap, uint64_t *n_segs_out,
                          uint64_t *blob_bytes_out, gemx_agg_row *preagg_out,
                          uint64_t preagg_cap, uint64_t *n_preagg_out) {
-  if (!s || op < GEMX_OP_COUNT || op > GEMX_OP_LAST) {
+  if (!s || !n_segs_out || !blob_bytes_out || op < GEMX_OP_COUNT ||
+      op > GEMX_OP_LAST) {
     seterr("downsample_write: bad arguments");
+    return GEMX_E_INVALID;
+  }
+  if (s->col_type == GEMX_TYPE_BOOL && op == GEMX_OP_SUM) {
+    seterr("downsample_write: boolean columns have no sum");
     return GEMX_E_INVALID;
   }
   /* per-series windows on device (the aggregate cursor output) */
@@ -901,11 +947,19 @@ static int ds_write_impl(gemx_shard *s, int64_t start_time,
       break;
     }
   }
-  rc = gemx_encode_shard(out_type, w_sid.data(), w_t.data(), w_v.data(),
+  /* a boolean output column takes one byte per row */
+  std::vector<uint8_t> w_b;
+  const void *w_vals = w_v.data();
+  if (out_type == GEMX_TYPE_BOOL) {
+    w_b.resize(n);
+    for (uint64_t i = 0; i < n; i++) w_b[i] = (uint8_t)(w_ok[i] && w_v[i] != 0);
+    w_vals = w_b.data();
+  }
+  rc = gemx_encode_shard(out_type, w_sid.data(), w_t.data(), w_vals,
                           w_ok.data(), n, seg_rows, blob_out, blob_cap,
                           descs_out, descs_cap, n_segs_out, blob_bytes_out);
   if (rc != 0 || !preagg_out || !n_preagg_out) return rc;
-  return w_preagg_build(out_type, w_sid.data(), w_t.data(), w_v.data(),
+  return w_preagg_build(out_type, w_sid.data(), w_t.data(), w_vals,
                         w_ok.data(), n, seg_rows, preagg_out, preagg_cap,
                         n_preagg_out);
 }
@@ -931,7 +985,7 @@ extern "C" int gemx_downsample_write_pre(
     uint64_t blob_cap, gemx_seg_desc *descs_out, uint64_t descs_cap,
     uint64_t *n_segs_out, uint64_t *blob_bytes_out, gemx_agg_row *preagg_out,
     uint64_t preagg_cap, uint64_t *n_preagg_out, int *out_type_out) {
-  if (!s || op < GEMX_OP_COUNT || op > GEMX_OP_LAST) {
+  if (!s || !n_segs_out || op < GEMX_OP_COUNT || op > GEMX_OP_LAST) {
     seterr("downsample_write: bad arguments");
     return GEMX_E_INVALID;
   }

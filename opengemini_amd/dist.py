@@ -24,7 +24,10 @@ keep first-processed), last = largest time (ties keep first-processed).
 Value slots are type-punned: for GEMX_TYPE_INT columns sum/min/max/
 first/last carry int64 BITS (viewed with .view(np.int64), never cast) and
 fold with int64 arithmetic/ordering, matching the reference's
-updateInteger* family; time slots always carry int64 bits.
+updateInteger* family; time slots always carry int64 bits. GEMX_TYPE_BOOL
+columns follow the int64 path on their 0/1 payloads (false < true,
+UpdateBooleanMin/Max/First/Last, reccord_functions.go); they have no sum,
+so the sum slot stays 0 on every shard.
 """
 
 import numpy as np
@@ -33,6 +36,8 @@ import torch.distributed as dist
 
 TYPE_INT = 1
 TYPE_FLOAT = 3
+TYPE_BOOL = 5
+_INT_PAYLOAD = (TYPE_INT, TYPE_BOOL)
 
 # partial layout per window (float64-typed tensor; int64 payloads — times
 # always, and every value slot for TYPE_INT — travel bit-exact via .view)
@@ -58,7 +63,7 @@ def window_partials(rows, interval, offset, w0, n_wins, col_type=TYPE_FLOAT):
     out[idx, C_COUNT] = rows["count"].astype(np.float64)
     valid = rows["min_isnil"] == 0
     fvalid = rows["first_isnil"] == 0
-    if col_type == TYPE_INT:
+    if col_type in _INT_PAYLOAD:
         # int64 value slots: carry the BITS (rows[...] fields are the
         # type-punned gemx_val / orc_val union viewed as int64 upstream)
         sum_i = np.asarray(rows["sum"]).view(np.int64)
@@ -99,7 +104,7 @@ def _fold(acc, nxt, col_type=TYPE_FLOAT):
     ni = nxt.view(np.int64)
     a_has = acc[:, C_HASMM] > 0
     n_has = nxt[:, C_HASMM] > 0
-    if col_type == TYPE_INT:
+    if col_type in _INT_PAYLOAD:
         ai[:, C_SUM] += ni[:, C_SUM]  # int64 add, Go wraparound semantics
         a_min, n_min = ai[:, C_MIN], ni[:, C_MIN]
         a_max, n_max = ai[:, C_MAX], ni[:, C_MAX]

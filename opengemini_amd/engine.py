@@ -26,6 +26,17 @@ _SRC = os.path.join(_DIR, "csrc", "gemx_engine.hip")
 
 GEMX_TYPE_INT = 1
 GEMX_TYPE_FLOAT = 3
+GEMX_TYPE_BOOL = 5
+
+
+def _int_operand(col_type, operand):
+    """filter_i for a compare against an int64 or boolean column (boolean
+    operands travel as 0/1)."""
+    if col_type == GEMX_TYPE_INT:
+        return int(operand)
+    if col_type == GEMX_TYPE_BOOL:
+        return int(bool(operand))
+    return 0
 
 # layouts mirror include/gemx.h (and are intentionally identical to the
 # oracle's, so parity tests can compare buffers field-by-field)
@@ -137,6 +148,10 @@ def _load():
     lib.gemx_fold_stats.argtypes = [
         C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
         C.POINTER(C.c_uint32),
+    ]
+    lib.gemx_bool_stats.restype = C.c_int
+    lib.gemx_bool_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
     ]
     lib.gemx_scan_agg_ex.restype = C.c_int
     lib.gemx_scan_agg_ex.argtypes = [
@@ -284,6 +299,9 @@ def encode_shard(col_type, sids, times, values, valid=None, seg_rows=1000,
     n = len(sids)
     if col_type == GEMX_TYPE_FLOAT:
         values = np.ascontiguousarray(values, dtype=np.float64)
+    elif col_type == GEMX_TYPE_BOOL:
+        # one byte per row; anything but 0/1 is refused by the writer
+        values = np.ascontiguousarray(values, dtype=np.uint8)
     else:
         values = np.ascontiguousarray(values, dtype=np.int64)
     vptr = None
@@ -481,7 +499,7 @@ class Shard:
             op_name, operand = filter
             fop = self.FILTER_OPS[op_name]
             ff = float(operand) if self.col_type == GEMX_TYPE_FLOAT else 0.0
-            fi = int(operand) if self.col_type == GEMX_TYPE_INT else 0
+            fi = _int_operand(self.col_type, operand)
             rc = lib.gemx_scan_agg_ex(
                 self._h, start_time, end_time, interval, offset,
                 1 if group_all else 0, fop, ff, fi,
@@ -513,6 +531,16 @@ class Shard:
         _check(self._lib.gemx_fold_stats(self._h, C.byref(f), C.byref(n),
                                          C.byref(r)), self._lib)
         return dict(folded=f.value, scanned=n.value, redone=bool(r.value))
+
+    def bool_stats(self):
+        """Routing of the last aggregate scan on a boolean shard:
+        (bitpar, other) = in-range segments reduced by the bit-parallel
+        kernel / by any other kernel. (0, 0) on non-boolean shards."""
+        b = C.c_uint64(0)
+        o = C.c_uint64(0)
+        _check(self._lib.gemx_bool_stats(self._h, C.byref(b), C.byref(o)),
+               self._lib)
+        return b.value, o.value
 
     def scan_agg_begin(self, start_time, end_time, interval, offset=0,
                        group_all=False, out_cap=None, buf_id=0):
@@ -640,7 +668,7 @@ class Shard:
         op_name, operand = filter
         fop = self.FILTER_OPS[op_name]
         ff = float(operand) if filter_shard.col_type == GEMX_TYPE_FLOAT else 0.0
-        fi = int(operand) if filter_shard.col_type == GEMX_TYPE_INT else 0
+        fi = _int_operand(filter_shard.col_type, operand)
         if out_cap is None:
             out_cap = self._rows_bound(interval, offset, group_all)
         out = self._pooled_out("agg", out_cap, AGG_ROW_DTYPE)
@@ -697,8 +725,7 @@ class Shard:
             arr[k].op = self.FILTER_OPS[op_name]
             arr[k].f = (float(operand)
                         if tgt.col_type == GEMX_TYPE_FLOAT else 0.0)
-            arr[k].i = (int(operand)
-                        if tgt.col_type == GEMX_TYPE_INT else 0)
+            arr[k].i = _int_operand(tgt.col_type, operand)
             arr[k].group = grp
         if out_cap is None:
             out_cap = self._rows_bound(interval, offset, group_all)
@@ -736,7 +763,7 @@ class Shard:
             op_name, operand = filter
             fop = self.FILTER_OPS[op_name]
             ff = float(operand) if self.col_type == GEMX_TYPE_FLOAT else 0.0
-            fi = int(operand) if self.col_type == GEMX_TYPE_INT else 0
+            fi = _int_operand(self.col_type, operand)
         n = C.c_uint64(0)
         st = _Stats()
         rc = lib.gemx_scan_agg_series(
@@ -791,7 +818,8 @@ class Shard:
         (blob, descs, preagg_rows, out_type): the write-side pre-agg
         rows (pre_aggregation.go:410 role) seed Shard.set_preagg on the
         re-attached output so covering preagg queries never scan.
-        op: count/sum/min/max/first/last; count yields an int64 column."""
+        op: count/sum/min/max/first/last; count yields an int64 column.
+        Boolean shards have no sum (GemxError)."""
         lib = self._lib
         opc = DOWNSAMPLE_OPS[op]
         n_rows = self._rows_bound(interval, offset, False)
