@@ -414,6 +414,42 @@ int gemx_prom_over_time(gemx_shard *, int64_t start_time, int64_t end_time,
                         gemx_rate_row *out_host, uint64_t cap, uint64_t *n_out,
                         gemx_query_stats *stats);
 
+/* top(field, N) / bottom(field, N) selector scans — the series-level
+ * top/bottom calls of the aggregate cursor (engine/series_call_processor.go:
+ * 56-78; heap reducers engine/series_agg_reducer.gen.go:1969-2146,
+ * 2327-2600; comparators engine/series_agg_func.gen.go:276-326, the same
+ * at the executor merge, engine/executor/agg_func.go:44-70).
+ * For every (series, window) over the non-nil rows with time in
+ * [start_time, end_time]: top keeps the n best points under "larger value,
+ * then earlier time", bottom under "smaller value, then earlier time";
+ * fewer than n points returns all, none returns nothing. A window's points
+ * are emitted time-ascending (equal times: top larger value first, bottom
+ * smaller first). Windows follow gemx_scan_agg's arithmetic (interval == 0:
+ * one window, win_start = start_time). Rows come grouped by sid in
+ * descriptor order, windows ascending. group_all = 1 selects the n best of
+ * the union of all series per window (sid = 0). Float NaN points are
+ * dropped before selection. Float and integer columns only:
+ * a boolean shard, n == 0, n > GEMX_TOPN_MAX, a bad sel or a NULL handle
+ * is GEMX_E_INVALID. GEMX_E_CAP when cap is below the rows produced (never
+ * more than n x the gemx_scan_agg row bound). Synchronous; its device
+ * state is separate from the aggregate plan, so it may be called while
+ * gemx_scan_agg_begin queries are in flight. stats may be NULL; merge_ms
+ * covers the per-series merge and, when grouped, the group stages. */
+#define GEMX_SEL_TOP 0
+#define GEMX_SEL_BOTTOM 1
+#define GEMX_TOPN_MAX 16
+typedef struct {
+  uint64_t sid;
+  int64_t win_start;
+  int64_t time;
+  gemx_val v;
+} gemx_point_row; /* 32 B */
+
+int gemx_scan_topn(gemx_shard *, int64_t start_time, int64_t end_time,
+                   int64_t interval, int64_t offset, int group_all, int sel,
+                   uint32_t n, gemx_point_row *out_host, uint64_t cap,
+                   uint64_t *n_out, gemx_query_stats *stats);
+
 /* ---------------- write side (downsample output) ----------------
  * The downsample service rewrites TSSP files with aggregated columns
  * (engine/engine_downsample.go via WriteIntoStorageTransform,
@@ -551,6 +587,16 @@ int gemx_rec_from_rows(const gemx_agg_row *rows, uint64_t n_rows,
                        const int *ops, int n_ops, int col_type,
                        void *const *val_bufs, uint8_t *const *bitmaps,
                        int64_t *time_out, gemx_colval *cols_out);
+
+/* Assemble the KeyCursor output record of a top/bottom call from point
+ * rows (appendCurrItem: one value and the point's own time per kept
+ * point): values pack dense, 8 bytes each, into val_buf (>= n_rows * 8
+ * bytes); every validity bit of bitmap (>= (n_rows+7)/8 bytes) is set and
+ * nil_count is 0; time_out receives the points' times. col_type is
+ * GEMX_TYPE_FLOAT or GEMX_TYPE_INT. Pure host code. */
+int gemx_rec_from_points(const gemx_point_row *rows, uint64_t n_rows,
+                         int col_type, void *val_buf, uint8_t *bitmap,
+                         int64_t *time_out, gemx_colval *col_out);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,8 @@ for CPU checking only.
 
 from .engine import (  # noqa: F401
     AGG_ROW_DTYPE,
+    POINT_ROW_DTYPE,
+    POINT_ROW_INT_DTYPE,
     SEG_DESC_DTYPE,
     GemxError,
     Shard,

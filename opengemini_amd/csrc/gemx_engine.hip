@@ -4512,6 +4512,8 @@ static void free_rate_plan(RatePlan &p) {
   p = RatePlan();
 }
 
+struct TopPlan; /* top/bottom selector state, gemx_topn.hpp */
+
 struct gemx_shard {
   int device;
   int col_type;
@@ -4612,6 +4614,7 @@ struct gemx_shard {
   const gemx_shard *x_checked = nullptr; /* alignment validated against */
   QueryPlan plan;
   RatePlan rate_plan;
+  TopPlan *top_plan = nullptr; /* built on the first gemx_scan_topn */
   /* pre-aggregation metadata (pre_aggregation.go FloatPreAgg role): one
    * whole-range aggregate row per series, computed on device once and
    * served for matchPreAgg-shaped queries whose range covers the series
@@ -5496,6 +5499,8 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
   return GEMX_OK;
 }
 
+static void free_top_plan(gemx_shard *s);
+
 extern "C" int gemx_shard_close(gemx_shard *s) {
   if (!s) return GEMX_OK;
   (void)hipSetDevice(s->device);
@@ -5508,6 +5513,7 @@ extern "C" int gemx_shard_close(gemx_shard *s) {
   free_plan(s->sub_plan);
   free_tag_plan(s->tag_plan);
   free_rate_plan(s->rate_plan);
+  free_top_plan(s);
   (void)hipFree(s->d_blob);
   (void)hipFree(s->d_descs);
   (void)hipFree(s->d_fast_ids);
@@ -7450,6 +7456,9 @@ extern "C" int gemx_prom_over_time(gemx_shard *s, int64_t start_time,
   return prom_rate_impl(s, start_time, end_time, range_ns, step_ns, 0, 0, func,
                         out_host, cap, n_out, stats);
 }
+
+/* ---------------- top(field, N) / bottom(field, N) ---------------- */
+#include "gemx_topn.hpp"
 
 /* ---------------- write side (downsample output) ---------------- */
 #include "gemx_writer.hpp"

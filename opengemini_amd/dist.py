@@ -153,3 +153,41 @@ def merge_across_shards(partials, device=None, group=None, col_type=TYPE_FLOAT):
     for r in range(1, world):
         acc = _fold(acc, gathered[r].cpu().numpy(), col_type=col_type)
     return acc
+
+
+def merge_topn(per_shard_rows, n, sel):
+    """Executor-side merge of top()/bottom() across shards — the same
+    comparators as the series-level heaps (engine/executor/agg_func.go:
+    44-70): folds the GROUPED point rows of several shards
+    (Shard.scan_topn(..., group_all=True)) into the final grouped rows.
+    Per win_start it keeps the best n of the union under "larger (top) /
+    smaller (bottom) value, then earlier time" and emits them
+    time-ascending (equal times: top larger value first, bottom smaller
+    first). The best n of the union are a subset of the shards' winners,
+    so no other traffic is needed. Pure numpy; rows keep the dtype of the
+    inputs (integer shards carry int64 values) and sid 0."""
+    if sel not in ("top", "bottom"):
+        raise ValueError("sel must be 'top' or 'bottom'")
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    parts = [np.asarray(r) for r in per_shard_rows]
+    if not parts:
+        raise ValueError("merge_topn needs at least one shard's rows")
+    rows = np.concatenate(parts)
+    if len(rows) == 0:
+        return rows
+    # value rank instead of the value itself: negating a rank is exact
+    # where negating an int64 (or comparing mixed -0.0/0.0) is not
+    _, vrank = np.unique(rows["value"], return_inverse=True)
+    vkey = -vrank.astype(np.int64) if sel == "top" else vrank.astype(np.int64)
+    win = rows["win_start"]
+    order = np.lexsort((rows["time"], vkey, win))
+    w_sorted = win[order]
+    first = np.concatenate([[True], w_sorted[1:] != w_sorted[:-1]])
+    start_idx = np.maximum.accumulate(np.where(first, np.arange(len(order)), 0))
+    keep = order[(np.arange(len(order)) - start_idx) < n]
+    emit = keep[np.lexsort((vkey[keep], rows["time"][keep], win[keep]))]
+    out = rows[emit].copy()
+    out["sid"] = 0
+    return out

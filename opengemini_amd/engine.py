@@ -85,6 +85,30 @@ RATE_ROW_DTYPE = np.dtype(
     [("sid", "<u8"), ("ts", "<i8"), ("value", "<f8"), ("isnil", "u1"), ("_pad", "u1", (7,))]
 )
 
+# one kept point of a top()/bottom() selector scan (gemx_point_row, 32 B).
+# The value slot is the type-punned gemx_val: float shards read it through
+# POINT_ROW_DTYPE, integer shards through POINT_ROW_INT_DTYPE (same bytes).
+POINT_ROW_DTYPE = np.dtype(
+    [("sid", "<u8"), ("win_start", "<i8"), ("time", "<i8"), ("value", "<f8")]
+)
+POINT_ROW_INT_DTYPE = np.dtype(
+    [("sid", "<u8"), ("win_start", "<i8"), ("time", "<i8"), ("value", "<i8")]
+)
+GEMX_SEL_TOP = 0
+GEMX_SEL_BOTTOM = 1
+GEMX_TOPN_MAX = 16
+TOPN_SELS = {"top": GEMX_SEL_TOP, "bottom": GEMX_SEL_BOTTOM}
+
+
+class _ColVal(C.Structure):
+    _fields_ = [
+        ("val", C.c_void_p),
+        ("bitmap", C.c_void_p),
+        ("bitmap_offset", C.c_int32),
+        ("len", C.c_int32),
+        ("nil_count", C.c_int32),
+    ]
+
 
 class _Stats(C.Structure):
     _fields_ = [
@@ -269,6 +293,17 @@ def _load():
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
         C.c_double, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
         C.POINTER(_Stats),
+    ]
+    lib.gemx_scan_topn.restype = C.c_int
+    lib.gemx_scan_topn.argtypes = [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+        C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+        C.POINTER(_Stats),
+    ]
+    lib.gemx_rec_from_points.restype = C.c_int
+    lib.gemx_rec_from_points.argtypes = [
+        C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(_ColVal),
     ]
     lib.gemx_prom_over_time.restype = C.c_int
     lib.gemx_prom_over_time.argtypes = [
@@ -519,6 +554,40 @@ class Shard:
         )
         return out[: n.value], stats
 
+    def scan_topn(self, start_time, end_time, interval, n, sel="top",
+                  offset=0, group_all=False, out_cap=None):
+        """top(field, n) / bottom(field, n) per GROUP BY time window: the n
+        best points per (series, window) — or, with group_all=True, of all
+        series together (sid 0) — under "larger (top) / smaller (bottom)
+        value, then earlier time", emitted time-ascending. Float and
+        integer shards only; NaN points are never selected.
+
+        Returns (rows, stats): rows in POINT_ROW_DTYPE, or
+        POINT_ROW_INT_DTYPE on an integer shard."""
+        lib = self._lib
+        if sel in TOPN_SELS:
+            sel = TOPN_SELS[sel]
+        if out_cap is None:
+            out_cap = max(int(n), 1) * self._rows_bound(interval, offset,
+                                                        group_all)
+        dt = (POINT_ROW_INT_DTYPE if self.col_type == GEMX_TYPE_INT
+              else POINT_ROW_DTYPE)
+        out = self._pooled_out("topn", max(out_cap, 1), POINT_ROW_DTYPE)
+        cnt = C.c_uint64(0)
+        st = _Stats()
+        rc = lib.gemx_scan_topn(
+            self._h, start_time, end_time, interval, offset,
+            1 if group_all else 0, int(sel), int(n),
+            out.ctypes.data_as(C.c_void_p), out_cap, C.byref(cnt),
+            C.byref(st),
+        )
+        _check(rc, lib)
+        stats = dict(
+            decode_ms=st.decode_ms, merge_ms=st.merge_ms, total_ms=st.total_ms,
+            host_ms=st.h2d_ms, points=st.points,
+            compressed_bytes=st.compressed_bytes, n_rows=st.n_rows,
+        )
+        return out[: cnt.value].view(dt), stats
 
     def fold_stats(self):
         """Wave-fold coverage of the last grouped query on this shard:
