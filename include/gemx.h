@@ -450,6 +450,48 @@ int gemx_scan_topn(gemx_shard *, int64_t start_time, int64_t end_time,
                    uint32_t n, gemx_point_row *out_host, uint64_t cap,
                    uint64_t *n_out, gemx_query_stats *stats);
 
+/* distinct(field) selector scans — the series-level distinct call of the
+ * aggregate cursor (engine/series_call_processor.go:56-78; floatDistinctItem
+ * / integerDistinctItem / booleanDistinctItem and the …DistinctReducer
+ * loops, engine/series_agg_reducer.gen.go:1583-1920; the executor twin
+ * DistinctItem[T], engine/executor/agg_iterator.go:284-332).
+ * For every (series, window) over the non-nil rows with time in
+ * [start_time, end_time]: every distinct value once, with the time of its
+ * first occurrence (its minimum time in the window); a window's rows are
+ * emitted by (time ascending, then value ascending). Windows follow
+ * gemx_scan_agg's arithmetic (interval == 0: one window, win_start =
+ * start_time; offset honoured). Rows come grouped by sid in descriptor
+ * order, windows ascending, dense (no gap rows); a window with no usable
+ * row emits nothing. Float, integer and boolean columns; boolean values
+ * travel as .i in {0,1}. group_all = 1: per window the distinct values of
+ * the union of all series, each with its earliest time over all series,
+ * sid = 0, same order.
+ * Deviations: float NaN points are dropped before the set is
+ * built; -0.0 is read as +0.0; the grouped time is the minimum time.
+ * At most GEMX_DISTINCT_MAX distinct values per output (series or group,
+ * window): a window that exceeds it fails the whole query with
+ * GEMX_E_UNSUPPORTED and a message naming the cap — nothing is truncated.
+ * The output count is data-dependent: on GEMX_E_CAP nothing is written to
+ * out_host and *n_out holds the number of rows the query produces, so the
+ * caller can size a retry. A NULL handle is GEMX_E_INVALID. Synchronous
+ * (host prefix sums between the tree levels); its device state is separate
+ * from the aggregate and top/bottom plans, so it may be called while
+ * gemx_scan_agg_begin queries are in flight. stats may be NULL: decode_ms
+ * covers the scan kernel, merge_ms the node levels (with the host's table
+ * building between them) and the emit. */
+#define GEMX_DISTINCT_MAX 2048
+int gemx_scan_distinct(gemx_shard *, int64_t start_time, int64_t end_time,
+                       int64_t interval, int64_t offset, int group_all,
+                       gemx_point_row *out_host, uint64_t cap,
+                       uint64_t *n_out, gemx_query_stats *stats);
+
+/* The shard's last distinct query: candidates = entries the scan kernel
+ * appended to its per-(segment, window) runs, points = non-nil in-range
+ * rows it scanned, levels = node levels run (level 0, the per-run unique,
+ * counts). Zeros before the first query. Any out pointer may be NULL. */
+int gemx_distinct_stats(gemx_shard *, uint64_t *candidates, uint64_t *points,
+                        uint32_t *levels);
+
 /* ---------------- write side (downsample output) ----------------
  * The downsample service rewrites TSSP files with aggregated columns
  * (engine/engine_downsample.go via WriteIntoStorageTransform,

@@ -12,6 +12,7 @@ from .engine import (  # noqa: F401
     POINT_ROW_DTYPE,
     POINT_ROW_INT_DTYPE,
     SEG_DESC_DTYPE,
+    GEMX_DISTINCT_MAX,
     GemxError,
     Shard,
     AggCursor,

@@ -948,6 +948,8 @@ struct DevErr {
                             unfolded when non-zero) */
   unsigned long long gaps; /* gap rows written by the merge kernels; the
                               host skips its compaction scan when zero */
+  unsigned int distinct_over; /* a distinct node produced more than
+                                 GEMX_DISTINCT_MAX values (gemx_distinct.hpp) */
 };
 
 __device__ __forceinline__ void set_err(DevErr *e, int code) {
@@ -4513,6 +4515,7 @@ static void free_rate_plan(RatePlan &p) {
 }
 
 struct TopPlan; /* top/bottom selector state, gemx_topn.hpp */
+struct DistinctPlan; /* distinct() state, gemx_distinct.hpp */
 
 struct gemx_shard {
   int device;
@@ -4615,6 +4618,7 @@ struct gemx_shard {
   QueryPlan plan;
   RatePlan rate_plan;
   TopPlan *top_plan = nullptr; /* built on the first gemx_scan_topn */
+  DistinctPlan *distinct_plan = nullptr; /* built on the first gemx_scan_distinct */
   /* pre-aggregation metadata (pre_aggregation.go FloatPreAgg role): one
    * whole-range aggregate row per series, computed on device once and
    * served for matchPreAgg-shaped queries whose range covers the series
@@ -5500,6 +5504,7 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
 }
 
 static void free_top_plan(gemx_shard *s);
+static void free_distinct_plan(gemx_shard *s);
 
 extern "C" int gemx_shard_close(gemx_shard *s) {
   if (!s) return GEMX_OK;
@@ -5514,6 +5519,7 @@ extern "C" int gemx_shard_close(gemx_shard *s) {
   free_tag_plan(s->tag_plan);
   free_rate_plan(s->rate_plan);
   free_top_plan(s);
+  free_distinct_plan(s);
   (void)hipFree(s->d_blob);
   (void)hipFree(s->d_descs);
   (void)hipFree(s->d_fast_ids);
@@ -7459,6 +7465,7 @@ extern "C" int gemx_prom_over_time(gemx_shard *s, int64_t start_time,
 
 /* ---------------- top(field, N) / bottom(field, N) ---------------- */
 #include "gemx_topn.hpp"
+#include "gemx_distinct.hpp"
 
 /* ---------------- write side (downsample output) ---------------- */
 #include "gemx_writer.hpp"

@@ -191,3 +191,39 @@ def merge_topn(per_shard_rows, n, sel):
     out = rows[emit].copy()
     out["sid"] = 0
     return out
+
+
+def merge_distinct(per_shard_rows):
+    """Executor-side merge of distinct() across shards (DistinctItem[T],
+    engine/executor/agg_iterator.go:284-332): folds the GROUPED point rows
+    of several shards (Shard.scan_distinct(..., group_all=True)) into the
+    final grouped rows. Per (win_start, value) it keeps the minimum time —
+    the engine's grouped time, a function of the data only — and emits each
+    window by (time, value). Every distinct value of the union is a
+    distinct value of some shard, so no other traffic is needed. Pure
+    numpy; rows keep the dtype of the inputs (integer and boolean shards
+    carry int64 values) and sid 0. -0.0 and 0.0 are one value (the engine
+    never emits -0.0)."""
+    parts = [np.asarray(r) for r in per_shard_rows]
+    if not parts:
+        raise ValueError("merge_distinct needs at least one shard's rows")
+    rows = np.concatenate(parts)
+    if len(rows) == 0:
+        return rows
+    val = rows["value"]
+    if val.dtype.kind == "f":
+        if np.isnan(val).any():
+            raise ValueError("merge_distinct: NaN is never a distinct value")
+        val = val + 0.0  # -0.0 -> 0.0
+    _, vrank = np.unique(val, return_inverse=True)
+    win = rows["win_start"]
+    order = np.lexsort((rows["time"], vrank, win))
+    w, r = win[order], vrank[order]
+    head = np.concatenate([[True], (w[1:] != w[:-1]) | (r[1:] != r[:-1])])
+    keep = order[head]
+    emit = keep[np.lexsort((vrank[keep], rows["time"][keep], win[keep]))]
+    out = rows[emit].copy()
+    out["sid"] = 0
+    if out["value"].dtype.kind == "f":
+        out["value"] = out["value"] + 0.0
+    return out

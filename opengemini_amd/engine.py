@@ -97,6 +97,9 @@ POINT_ROW_INT_DTYPE = np.dtype(
 GEMX_SEL_TOP = 0
 GEMX_SEL_BOTTOM = 1
 GEMX_TOPN_MAX = 16
+GEMX_DISTINCT_MAX = 2048
+GEMX_E_UNSUPPORTED = -4
+GEMX_E_CAP = -6
 TOPN_SELS = {"top": GEMX_SEL_TOP, "bottom": GEMX_SEL_BOTTOM}
 
 
@@ -299,6 +302,16 @@ def _load():
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
         C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
         C.POINTER(_Stats),
+    ]
+    lib.gemx_scan_distinct.restype = C.c_int
+    lib.gemx_scan_distinct.argtypes = [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_Stats),
+    ]
+    lib.gemx_distinct_stats.restype = C.c_int
+    lib.gemx_distinct_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint32),
     ]
     lib.gemx_rec_from_points.restype = C.c_int
     lib.gemx_rec_from_points.argtypes = [
@@ -588,6 +601,62 @@ class Shard:
             compressed_bytes=st.compressed_bytes, n_rows=st.n_rows,
         )
         return out[: cnt.value].view(dt), stats
+
+    def scan_distinct(self, start_time, end_time, interval, offset=0,
+                      group_all=False, out_cap=None):
+        """distinct(field) per GROUP BY time window: every distinct value of
+        a (series, window) once, with the time of its first occurrence —
+        or, with group_all=True, of all series together (sid 0, earliest
+        time over all series) — emitted by (time, value). Float, integer
+        and boolean shards; NaN points are dropped and -0.0 reads as 0.0.
+        More than GEMX_DISTINCT_MAX distinct values in one output window
+        raise GemxError (GEMX_E_UNSUPPORTED): nothing is truncated.
+
+        The row count depends on the data: with out_cap=None the call
+        starts from the scan_topn bound for n = 8 and, when that is too
+        small, retries once with the count the engine reports.
+
+        Returns (rows, stats): rows in POINT_ROW_DTYPE, or
+        POINT_ROW_INT_DTYPE on an integer or boolean shard."""
+        lib = self._lib
+        retry = out_cap is None
+        if out_cap is None:
+            out_cap = 8 * self._rows_bound(interval, offset, group_all)
+        dt = (POINT_ROW_DTYPE if self.col_type == GEMX_TYPE_FLOAT
+              else POINT_ROW_INT_DTYPE)
+        cnt = C.c_uint64(0)
+        st = _Stats()
+        while True:
+            out = self._pooled_out("distinct", max(out_cap, 1),
+                                   POINT_ROW_DTYPE)
+            rc = lib.gemx_scan_distinct(
+                self._h, start_time, end_time, interval, offset,
+                1 if group_all else 0, out.ctypes.data_as(C.c_void_p),
+                out_cap, C.byref(cnt), C.byref(st),
+            )
+            if rc == GEMX_E_CAP and retry:
+                retry = False
+                out_cap = int(cnt.value)
+                continue
+            break
+        _check(rc, lib)
+        stats = dict(
+            decode_ms=st.decode_ms, merge_ms=st.merge_ms, total_ms=st.total_ms,
+            host_ms=st.h2d_ms, points=st.points,
+            compressed_bytes=st.compressed_bytes, n_rows=st.n_rows,
+        )
+        return out[: cnt.value].view(dt), stats
+
+    def distinct_stats(self):
+        """The last scan_distinct on this shard: dict(candidates=<entries
+        the scan kernel appended>, points=<non-nil in-range rows scanned>,
+        levels=<node levels run, level 0 included>)."""
+        c = C.c_uint64(0)
+        p = C.c_uint64(0)
+        lv = C.c_uint32(0)
+        _check(self._lib.gemx_distinct_stats(self._h, C.byref(c), C.byref(p),
+                                             C.byref(lv)), self._lib)
+        return dict(candidates=c.value, points=p.value, levels=lv.value)
 
     def fold_stats(self):
         """Wave-fold coverage of the last grouped query on this shard:
