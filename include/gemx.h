@@ -174,6 +174,23 @@ int gemx_scan_agg_grouped(gemx_shard *, int64_t start_time, int64_t end_time,
 int gemx_fold_stats(gemx_shard *, uint64_t *folded_segments,
                     uint64_t *scanned_segments, uint32_t *redone);
 
+/* Row split of the folded waves in the shard's last grouped query. A
+ * folding wave's windows are cut into up to 8 contiguous runs, each a
+ * wave-task of its own that resumes the decode from a checkpoint recorded
+ * at attach (every 32 rows), so the launch fills the chip; rows are
+ * bit-identical to the unsplit fold. *k_max is the largest number of runs
+ * any folding wave was cut into (1: folded, not split; 0: the query did not
+ * fold), *tasks the wave-tasks launched (runs of folding waves plus one per
+ * non-folding wave), *skipped_rows the records decoded only to get from a
+ * checkpoint to a run's first row, summed over tasks (per lane). A run
+ * never has fewer than 2 windows or 64 rows. GEMX_FOLD_SPLIT=K, read at
+ * attach, forces the number of runs (1 = off, at most 8); unset, the policy
+ * picks one nearly full resident round of tasks (4 waves per SIMD) where
+ * the wave count allows it, else about 2 1/4 rounds. Any out pointer may
+ * be NULL. */
+int gemx_fold_split_stats(gemx_shard *, uint32_t *k_max, uint32_t *tasks,
+                          uint64_t *skipped_rows);
+
 /* Routing of the shard's last aggregate scan on a boolean column: how many
  * in-range segments the bit-parallel kernel (k_scan_bool_grid: full blocks
  * on a const-delta time grid, interval > 0, no own-column predicate, not

@@ -1295,10 +1295,35 @@ __global__ void __launch_bounds__(256) k_scan_fast(
  * position / 64. fidx < 0: the wave runs the per-segment Partial path. */
 struct FoldWave {
   int32_t fidx;    /* column in the [window][folded wave] GAcc array */
-  uint32_t tab;    /* offset of this wave's row-boundary table */
+  uint32_t tab;    /* offset of this task's row-boundary table */
   uint32_t n_wins; /* windows covered; table holds n_wins + 1 entries */
   uint32_t wrel;   /* first window, relative to the plan's W0 */
+  /* row split: a folding wave is cut into contiguous window runs, one
+   * wave-task each (tab / n_wins / wrel then describe the run). A run that
+   * does not start at row 0 resumes the decode from checkpoint `ckpt` and
+   * decodes `skip` records to reach its first row. */
+  uint32_t wave;  /* launch-list wave: lanes are entries wave*64 .. +63 */
+  uint32_t ckpt;  /* checkpoint index (row ckpt * GEMX_GOR_CKPT_ROWS) */
+  uint32_t skip;  /* records between the checkpoint row and the first row */
+  uint32_t flags; /* FOLD_SUB_FIRST | FOLD_SUB_LAST */
 };
+#define FOLD_SUB_FIRST 1u /* starts at row 0 from GorDesc.first_val */
+#define FOLD_SUB_LAST 2u  /* owns the last window: checks the terminator */
+
+/* Decoder resume state of one gorilla stream after row c * S
+ * (S = GEMX_GOR_CKPT_ROWS), recorded once at attach by k_gor_ckpt: the
+ * state a lane of k_scan_grid_gor holds between two GOR_NEXT()s. Entry c of
+ * the segment in slot j of a 64-slot launch group sits at
+ * ck_base + c * 64, so a wave loads one checkpoint row coalesced. */
+#ifndef GEMX_GOR_CKPT_ROWS
+#define GEMX_GOR_CKPT_ROWS 32
+#endif
+struct __attribute__((aligned(16))) GorCkpt {
+  uint64_t g_val;    /* value bits of row c * S */
+  uint32_t word_idx; /* stream word under w0 */
+  uint8_t bp, mean, trail, _pad;
+};
+static_assert(sizeof(GorCkpt) == 16, "GorCkpt is one 16-byte load");
 
 /* one lane's window result inside a folded wave; times travel as row
  * indices because (t0, dt) are wave-uniform */
@@ -1434,14 +1459,22 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
     uint32_t nseg_ids, Partial *__restrict__ partials, int64_t interval,
     int64_t offset, DevErr *err, const FoldWave *__restrict__ fwaves,
     const uint32_t *__restrict__ fbounds, GAcc *__restrict__ fold_out,
-    uint32_t n_fold) {
+    uint32_t n_fold, uint32_t n_tasks, const uint32_t *__restrict__ ck_base,
+    const GorCkpt *__restrict__ ckpts) {
   uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  /* FOLD keeps the absent lanes of the last wave in the loop: a folded
-   * wave reduces across all 64 lanes */
-  for (uint32_t li = gid; FOLD ? ((li & ~63u) < nseg_ids) : (li < nseg_ids);
-       li += gridDim.x * blockDim.x) {
+  /* FOLD strides over the plan's wave-tasks (one per non-folding wave, one
+   * per row-split run of a folding wave; blockDim is a multiple of 64) and
+   * keeps the absent lanes of the last wave in the loop: a folded wave
+   * reduces across all 64 lanes */
+  const uint32_t n_it = FOLD ? n_tasks : nseg_ids;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t it = FOLD ? (gid >> 6) : gid; it < n_it;
+       it += FOLD ? (stride >> 6) : stride) {
+    uint32_t li = it;
     if (FOLD) {
-      const FoldWave fw = fwaves[li >> 6];
+      const FoldWave fw = fwaves[it];
+      li = (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.wave) * 64 +
+           (threadIdx.x & 63);
       const int fidx = __builtin_amdgcn_readfirstlane(fw.fidx);
       if (fidx >= 0) {
         /* ---- folded wave: the 64 segments share (t0, dt, rows), so every
@@ -1463,20 +1496,52 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
         GAcc *orow = fold_out +
                      (uint64_t)__builtin_amdgcn_readfirstlane((int)fw.wrel) * n_fold +
                      (uint32_t)fidx;
-        uint64_t g_val = g.first_val;
-        if (g_val == UVNAN) set_err(err, GEMX_E_DECODE); /* decode stays
-            inside the arena pad; the result is discarded */
+        const uint32_t flags =
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.flags);
+        uint64_t g_val;
         GorA br;
-        br.init(arena, g.arena_base);
-        uint32_t g_mean = 64, g_trail = 0;
+        uint32_t g_mean, g_trail;
         uint64_t bad = 0;
-        uint32_t i = 0;
+        if (flags & FOLD_SUB_FIRST) {
+          g_val = g.first_val;
+          if (g_val == UVNAN) set_err(err, GEMX_E_DECODE); /* decode stays
+              inside the arena pad; the result is discarded */
+          br.init(arena, g.arena_base);
+          g_mean = 64;
+          g_trail = 0;
+        } else {
+          /* Resume at the checkpoint below this run's first row. The
+           * checkpoint came from the same deterministic decode, so the
+           * runs of a wave together read exactly the records the unsplit
+           * wave reads, and every record is counted into some run's `bad`
+           * (the checkpoint row's own value is counted here: with skip == 0
+           * no run decodes it). A corrupt stream cannot push a run past
+           * GEMX_ARENA_PAD_WORDS either: checkpoint c was reached in c*S
+           * records of at most two word-advances each, and the run decodes
+           * at most the rows that remain after it plus the terminator, so
+           * cursor + prefetch stay under the whole-stream bound the pad is
+           * sized for. */
+          const GorCkpt ck =
+              ckpts[ck_base[si] +
+                    (uint64_t)__builtin_amdgcn_readfirstlane((int)fw.ckpt) * 64];
+          g_val = ck.g_val;
+          br.init(arena, g.arena_base + (uint64_t)ck.word_idx * 64);
+          br.bp = ck.bp;
+          g_mean = ck.mean;
+          g_trail = ck.trail;
+          bad += (uint64_t)(g_val == UVNAN);
+          for (uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.skip);
+               q; q--)
+            GOR_NEXT();
+        }
+        uint32_t i = bt[0]; /* this run's first row */
+        bool pending = false; /* value of row i not decoded yet */
         for (uint32_t k = 0; k < nw; k++, orow += n_fold) {
           const uint32_t gend = bt[k + 1];
           if (gend <= i) continue; /* empty window: slot stays unused */
-          if (i != 0) GOR_NEXT();
-          double fv;
-          memcpy(&fv, &g_val, 8);
+          if (pending) GOR_NEXT();
+          pending = true;
+          const double fv = __longlong_as_double((long long)g_val);
           FoldLane a;
           a.sum = fv;
           a.mn = fv;
@@ -1487,8 +1552,7 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
           a.max_row = i;
           for (uint32_t r = i + 1; r < gend; r++) {
             GOR_NEXT();
-            double v;
-            memcpy(&v, &g_val, 8);
+            const double v = __longlong_as_double((long long)g_val);
             a.sum += v;
             if (a.mn > v) { a.mn = v; a.min_row = r; }
             if (a.mx < v) { a.mx = v; a.max_row = r; }
@@ -1521,8 +1585,14 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
           }
           i = gend;
         }
-        GOR_NEXT();
-        if (bad != 1 || g_val != UVNAN) set_err(err, GEMX_E_DECODE);
+        /* the run that owns the last window checks the terminator; every
+         * other run only requires its own records to be uvnan-free */
+        if (flags & FOLD_SUB_LAST) {
+          GOR_NEXT();
+          if (bad != 1 || g_val != UVNAN) set_err(err, GEMX_E_DECODE);
+        } else if (bad != 0) {
+          set_err(err, GEMX_E_DECODE);
+        }
         continue;
       }
       if (li >= nseg_ids) continue;
@@ -1569,15 +1639,13 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
       }
       if (!first_pending) GOR_NEXT();
       first_pending = 0;
-      double fv;
-      memcpy(&fv, &g_val, 8);
+      const double fv = __longlong_as_double((long long)g_val);
       double sf = fv, mn = fv, mx = fv, lastv = fv;
       const double firstv = fv;
       int min_row = i, max_row = i;
       for (int k = i + 1; k < gend; k++) {
         GOR_NEXT();
-        double v;
-        memcpy(&v, &g_val, 8);
+        const double v = __longlong_as_double((long long)g_val);
         sf += v;
         /* first-occurrence-wins strict compares (column_util.go:204-209);
          * NaN compares false -> never replaces (Go parity) */
@@ -1613,6 +1681,50 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
     }
   }
 }
+
+/* Attach-time checkpoint walk: one lane per gorilla-list segment in launch
+ * (= arena slot) order, the scan's own record step, state written every
+ * GEMX_GOR_CKPT_ROWS rows (see GorCkpt). No validation here: the scan
+ * validates every record it decodes, and a corrupt stream stays inside the
+ * arena pad for the same reason the scan does. The host sized the table so
+ * that entries 0 .. (rows - 1) / S of every segment exist. Records the
+ * rotating reader's cursor; the batch-refill A/B build has no checkpoints
+ * and folds unsplit. */
+#if !GEMX_GOR_BATCH_REFILL
+__global__ void __launch_bounds__(256) k_gor_ckpt(
+    const uint64_t *__restrict__ arena, const GorDesc *__restrict__ gors,
+    const uint32_t *__restrict__ seg_ids, const uint32_t *__restrict__ seg_rows,
+    uint32_t nseg_ids, const uint32_t *__restrict__ ck_base,
+    GorCkpt *__restrict__ ckpts) {
+  const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+  if (li >= nseg_ids) return;
+  const uint32_t si = seg_ids[li];
+  const GorDesc g = gors[si];
+  const uint32_t rows = seg_rows[li];
+  if (rows == 0) return;
+  const uint32_t last = (rows - 1) / GEMX_GOR_CKPT_ROWS;
+  GorCkpt *out = ckpts + ck_base[si];
+  uint64_t g_val = g.first_val;
+  GorA br;
+  br.init(arena, g.arena_base);
+  uint32_t g_mean = 64, g_trail = 0;
+  uint64_t bad = 0;
+  for (uint32_t c = 0;; c++, out += 64) {
+    GorCkpt ck;
+    ck.g_val = g_val;
+    /* p tracks the address of L, four words past w0 */
+    ck.word_idx = (uint32_t)((br.p - (arena + g.arena_base)) >> 6) - 4;
+    ck.bp = (uint8_t)br.bp;
+    ck.mean = (uint8_t)g_mean;
+    ck.trail = (uint8_t)g_trail;
+    ck._pad = 0;
+    *out = ck;
+    if (c == last) break;
+    for (int r = 0; r < GEMX_GOR_CKPT_ROWS; r++) GOR_NEXT();
+  }
+  (void)bad;
+}
+#endif
 
 #undef GOR_NEXT
 
@@ -1689,15 +1801,13 @@ __global__ void __launch_bounds__(256) k_scan_gor_sub(
       }
       if (!first_pending) GOR_NEXT();
       first_pending = 0;
-      double fv;
-      memcpy(&fv, &g_val, 8);
+      const double fv = __longlong_as_double((long long)g_val);
       double sf = fv, mn = fv, mx = fv, lastv = fv;
       const double firstv = fv;
       int min_row = i, max_row = i;
       for (int k = i + 1; k < gend; k++) {
         GOR_NEXT();
-        double v;
-        memcpy(&v, &g_val, 8);
+        const double v = __longlong_as_double((long long)g_val);
         sf += v;
         if (mn > v) { mn = v; min_row = k; }
         if (mx < v) { mx = v; max_row = k; }
@@ -4454,6 +4564,9 @@ struct QueryPlan {
   uint32_t *d_p1_sel = nullptr;    /* series with a non-folded segment */
   uint32_t n_fold_waves = 0, n_p1_sel = 0, fsplit = 1, fper_chunk = 1;
   uint64_t fold_segs = 0, scan_segs = 0;
+  /* row split of the folding waves: d_fwaves holds n_fold_tasks wave-tasks */
+  uint32_t n_fold_tasks = 0, split_kmax = 0;
+  uint64_t split_skipped = 0;
   bool fold_off = false; /* set after a NaN redo: stay unfolded */
 };
 
@@ -4545,6 +4658,13 @@ struct gemx_shard {
   GorDesc *d_gor = nullptr;
   uint64_t *d_arena = nullptr; /* lane-interleaved gorilla stream arena */
   uint64_t arena_words = 0;
+  /* decoder checkpoints for the row split of folded waves (see GorCkpt):
+   * built on the device at attach for shards that can fold, else null */
+  GorCkpt *d_ckpt = nullptr;
+  uint32_t *d_ck_base = nullptr; /* per segment: entry 0 of its column */
+  uint32_t fold_split_forced = 0; /* GEMX_FOLD_SPLIT at attach; 0 = policy */
+  uint32_t last_split_kmax = 0, last_split_tasks = 0;
+  uint64_t last_split_skipped = 0;
   /* series grouping: ranges in desc order */
   struct SeriesRange {
     uint64_t sid;
@@ -4928,6 +5048,62 @@ static int host_gor_walk(const uint8_t *stream, uint64_t stream_bytes,
 #endif
 #define GEMX_SUB_MIN_ROWS 64
 
+#include "gemx_foldsplit.hpp"
+
+/* Decoder checkpoints for the row split of folded waves, built on the
+ * device right after the arena upload (a host walk reads one bit at a time
+ * and would add seconds to a 100M-point attach). The table is laid out like
+ * the arena: the 64 slots of a launch group interleaved, one row of 64
+ * entries per checkpoint, sized by the group's longest segment. Segment
+ * data is immutable after attach, so this runs once per shard. */
+static int build_gor_ckpts(gemx_shard *s) {
+#if GEMX_GOR_BATCH_REFILL
+  (void)s;
+  return GEMX_OK;
+#else
+  const size_t n = s->fast_gor_ids.size();
+  std::vector<uint32_t> base(s->nsegs ? s->nsegs : 1, 0);
+  uint64_t total = 0;
+  for (size_t g0 = 0; g0 < n; g0 += 64) {
+    const size_t ge = std::min(g0 + 64, n);
+    uint64_t maxc = 1;
+    for (size_t j = g0; j < ge; j++) {
+      const uint32_t rows = s->h_descs[s->fast_gor_ids[j]].rows;
+      if (rows) maxc = std::max<uint64_t>(maxc, (rows - 1) / GEMX_GOR_CKPT_ROWS + 1);
+    }
+    if (total + maxc * 64 > UINT32_MAX) return GEMX_OK; /* no table: waves
+        of this shard fold unsplit */
+    for (size_t j = g0; j < ge; j++)
+      base[s->fast_gor_ids[j]] = (uint32_t)(total + (j - g0));
+    total += maxc * 64;
+  }
+  uint32_t *d_ids = nullptr;
+  HIP_CHECK(hipMalloc(&s->d_ckpt, sizeof(GorCkpt) * total));
+  HIP_CHECK(hipMemset(s->d_ckpt, 0, sizeof(GorCkpt) * total));
+  HIP_CHECK(hipMalloc(&s->d_ck_base, sizeof(uint32_t) * base.size()));
+  HIP_CHECK(hipMemcpy(s->d_ck_base, base.data(), sizeof(uint32_t) * base.size(),
+                      hipMemcpyHostToDevice));
+  /* launch list and row counts (the shard's device copies of both are
+   * uploaded later in attach) */
+  std::vector<uint32_t> ids_rows(s->fast_gor_ids);
+  for (size_t j = 0; j < n; j++)
+    ids_rows.push_back(s->h_descs[s->fast_gor_ids[j]].rows);
+  HIP_CHECK(hipMalloc(&d_ids, sizeof(uint32_t) * 2 * n));
+  hipError_t e = hipMemcpy(d_ids, ids_rows.data(), sizeof(uint32_t) * 2 * n,
+                           hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_gor_ckpt, dim3((uint32_t)((n + 255) / 256)), dim3(256),
+                       0, 0, s->d_arena, s->d_gor, d_ids, d_ids + n,
+                       (uint32_t)n, s->d_ck_base, s->d_ckpt);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  (void)hipFree(d_ids);
+  HIP_CHECK(e);
+  return GEMX_OK;
+#endif
+}
+
 static int build_gor_arena(gemx_shard *s, const uint8_t *blob) {
   size_t n = s->fast_gor_ids.size();
   /* arena_base sentinel ~0: "this segment has no arena slot" (slot 0 is
@@ -5114,6 +5290,14 @@ static int build_gor_arena(gemx_shard *s, const uint8_t *blob) {
   }
   HIP_CHECK(hipMemcpy(s->d_gor, s->h_gor.data(), sizeof(GorDesc) * s->nsegs,
                       hipMemcpyHostToDevice));
+  /* shards whose grouped scans fold (not split-sized, or asked to fold
+   * anyway) get decoder checkpoints so the fold plan can split waves by
+   * rows */
+  if (n > 0 && !s->fold_disabled &&
+      (n >= GEMX_SPLIT_MIN_LANES || s->fold_underfilled)) {
+    int crc = build_gor_ckpts(s);
+    if (crc != GEMX_OK) return crc;
+  }
   /* underfilled gorilla grid (config #1 shape: few deep segments): walk
    * the streams once on the host and record per-sub resume states so the
    * scan can run one lane per SUB-segment */
@@ -5395,6 +5579,10 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
 
   s->fold_disabled = getenv("GEMX_DISABLE_FOLD") != nullptr;
   s->fold_underfilled = getenv("GEMX_FOLD_UNDERFILLED") != nullptr;
+  if (const char *fs = getenv("GEMX_FOLD_SPLIT")) {
+    const long k = strtol(fs, nullptr, 10);
+    s->fold_split_forced = (uint32_t)(k < 1 ? 1 : (k > 8 ? 8 : k));
+  }
   s->ser_disjoint.assign(s->series_ranges.size(), 1);
   for (size_t g = 0; g < s->series_ranges.size(); g++) {
     const auto &r = s->series_ranges[g];
@@ -5409,6 +5597,8 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
        * catastrophe) — free them before dropping the handle */
       if (s->d_gor) (void)hipFree(s->d_gor);
       if (s->d_arena) (void)hipFree(s->d_arena);
+      if (s->d_ckpt) (void)hipFree(s->d_ckpt);
+      if (s->d_ck_base) (void)hipFree(s->d_ck_base);
       if (s->d_subs) (void)hipFree(s->d_subs);
       if (s->d_sub_start) (void)hipFree(s->d_sub_start);
       if (s->d_sub_count) (void)hipFree(s->d_sub_count);
@@ -5533,6 +5723,8 @@ extern "C" int gemx_shard_close(gemx_shard *s) {
   if (s->d_sub_count) (void)hipFree(s->d_sub_count);
   if (s->d_gor) (void)hipFree(s->d_gor);
   if (s->d_arena) (void)hipFree(s->d_arena);
+  if (s->d_ckpt) (void)hipFree(s->d_ckpt);
+  if (s->d_ck_base) (void)hipFree(s->d_ck_base);
   (void)hipFree(s->d_general_ids);
   if (s->d_row_base) (void)hipFree(s->d_row_base);
   if (s->d_xbm) (void)hipFree(s->d_xbm);
@@ -5904,7 +6096,8 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                s->h_descs[si].rows == rows && P.segq[si].w_first == wf &&
                P.segq[si].n_wins == nw && ser_ok[P.segq[si].series_idx];
         }
-        fw[wv] = {-1, 0, 0, 0};
+        fw[wv] = {-1, 0, 0, 0, (uint32_t)wv, 0, 0,
+                  FOLD_SUB_FIRST | FOLD_SUB_LAST};
         if (!ok) continue;
         auto key = std::make_tuple(t0, dt, rows);
         auto it = tabs.find(key);
@@ -5919,7 +6112,10 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
           }
           it = tabs.emplace(key, off).first;
         }
-        fw[wv] = {(int32_t)nfold++, it->second, nw, (uint32_t)(wf - P.W0)};
+        fw[wv].fidx = (int32_t)nfold++;
+        fw[wv].tab = it->second;
+        fw[wv].n_wins = nw;
+        fw[wv].wrel = (uint32_t)(wf - P.W0);
         for (size_t j = a; j < b; j++) folded[gl[j]] = 1;
         P.fold_segs += b - a;
       }
@@ -5944,9 +6140,51 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
           P.fper_chunk = (uint32_t)pc;
           P.fsplit = (uint32_t)((sel.size() + pc - 1) / pc); /* <= gsplit */
         }
-        HIP_CHECK(hipMalloc(&P.d_fwaves, sizeof(FoldWave) * fw.size()));
-        HIP_CHECK(hipMemcpyAsync(P.d_fwaves, fw.data(),
-                                 sizeof(FoldWave) * fw.size(),
+        /* row split: cut each folding wave's window list into up to K
+         * runs (gemx_foldsplit.hpp) so the launch fills the chip; a wave
+         * without checkpoints, or too short to cut, stays one task, and so
+         * does every non-folding wave. Tasks are ordered run-major, so the
+         * runs of one wave are spread over the launch and neighbouring
+         * tasks read neighbouring arena groups. */
+        const uint32_t K =
+            s->d_ckpt ? fold_split_k(fw.size(), s->fold_split_forced) : 1;
+        std::vector<uint32_t> cuts(fw.size() * (size_t)(K + 1), 0);
+        std::vector<uint32_t> runs(fw.size(), 1);
+        for (size_t wv = 0; wv < fw.size(); wv++)
+          if (fw[wv].fidx >= 0 && K > 1)
+            runs[wv] = fold_split_cuts(bounds.data() + fw[wv].tab,
+                                       fw[wv].n_wins, K, GEMX_GOR_CKPT_ROWS,
+                                       GEMX_SUB_MIN_ROWS,
+                                       &cuts[wv * (size_t)(K + 1)]);
+        std::vector<FoldWave> tasks;
+        tasks.reserve(fw.size() * (size_t)K);
+        P.split_kmax = 0;
+        P.split_skipped = 0;
+        for (uint32_t j = 0; j < K; j++)
+          for (size_t wv = 0; wv < fw.size(); wv++) {
+            if (j >= runs[wv]) continue;
+            FoldWave t = fw[wv];
+            if (t.fidx >= 0) P.split_kmax = std::max(P.split_kmax, runs[wv]);
+            if (runs[wv] > 1) {
+              const uint32_t *c = &cuts[wv * (size_t)(K + 1)];
+              const uint32_t r0 = bounds[fw[wv].tab + c[j]];
+              t.tab += c[j];
+              t.n_wins = c[j + 1] - c[j];
+              t.wrel += c[j];
+              t.flags = (j == 0 ? FOLD_SUB_FIRST : 0u) |
+                        (j + 1 == runs[wv] ? FOLD_SUB_LAST : 0u);
+              if (j > 0) {
+                t.ckpt = r0 / GEMX_GOR_CKPT_ROWS;
+                t.skip = r0 % GEMX_GOR_CKPT_ROWS;
+                P.split_skipped += t.skip;
+              }
+            }
+            tasks.push_back(t);
+          }
+        P.n_fold_tasks = (uint32_t)tasks.size();
+        HIP_CHECK(hipMalloc(&P.d_fwaves, sizeof(FoldWave) * tasks.size()));
+        HIP_CHECK(hipMemcpyAsync(P.d_fwaves, tasks.data(),
+                                 sizeof(FoldWave) * tasks.size(),
                                  hipMemcpyHostToDevice, s->stream));
         HIP_CHECK(hipMalloc(&P.d_fbounds, sizeof(uint32_t) * bounds.size()));
         HIP_CHECK(hipMemcpyAsync(P.d_fbounds, bounds.data(),
@@ -6050,6 +6288,9 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     s->last_fold_folded = fold ? P.fold_segs : 0;
     s->last_fold_scanned = P.scan_segs;
     s->last_fold_redo = redo_slot >= 0;
+    s->last_split_kmax = fold ? P.split_kmax : 0;
+    s->last_split_tasks = fold ? P.n_fold_tasks : 0;
+    s->last_split_skipped = fold ? P.split_skipped : 0;
   }
   struct FastLaunch {
     const uint32_t *list;
@@ -6107,18 +6348,25 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                              P.d_subpart);
         continue;
       }
-      if (fold)
-        hipLaunchKernelGGL(k_scan_grid_gor<true>, dim3(blocks), dim3(tpb), 0,
+      if (fold) {
+        /* one wave per task of the fold plan */
+        const uint64_t flanes = (uint64_t)P.n_fold_tasks * 64;
+        const uint32_t ftpb = (flanes < 64 * 1024) ? 64 : (uint32_t)TPB;
+        const uint32_t fblocks =
+            (uint32_t)std::min<uint64_t>((flanes + ftpb - 1) / ftpb, 65535);
+        hipLaunchKernelGGL(k_scan_grid_gor<true>, dim3(fblocks), dim3(ftpb), 0,
                            s->stream, s->d_arena, s->arena_words, s->d_gor,
                            s->d_descs, d_segq, lst, n, d_part, interval,
                            offset, d_err, P.d_fwaves, P.d_fbounds,
-                           (GAcc *)P.d_fold, P.n_fold_waves);
-      else
+                           (GAcc *)P.d_fold, P.n_fold_waves, P.n_fold_tasks,
+                           s->d_ck_base, s->d_ckpt);
+      } else
         hipLaunchKernelGGL(k_scan_grid_gor<false>, dim3(blocks), dim3(tpb), 0,
                            s->stream, s->d_arena, s->arena_words, s->d_gor,
                            s->d_descs, d_segq, lst, n, d_part, interval,
                            offset, d_err, (const FoldWave *)nullptr,
-                           (const uint32_t *)nullptr, (GAcc *)nullptr, 0u);
+                           (const uint32_t *)nullptr, (GAcc *)nullptr, 0u, 0u,
+                           (const uint32_t *)nullptr, (const GorCkpt *)nullptr);
       continue;
     }
     if (launches[li].gridp == 3) { /* lane per raw segment, arena-fed */
@@ -6491,6 +6739,15 @@ extern "C" int gemx_fold_stats(gemx_shard *s, uint64_t *folded_segments,
   if (folded_segments) *folded_segments = s->last_fold_folded;
   if (scanned_segments) *scanned_segments = s->last_fold_scanned;
   if (redone) *redone = s->last_fold_redo;
+  return GEMX_OK;
+}
+
+extern "C" int gemx_fold_split_stats(gemx_shard *s, uint32_t *k_max,
+                                     uint32_t *tasks, uint64_t *skipped_rows) {
+  if (!s) return GEMX_E_INVALID;
+  if (k_max) *k_max = s->last_split_kmax;
+  if (tasks) *tasks = s->last_split_tasks;
+  if (skipped_rows) *skipped_rows = s->last_split_skipped;
   return GEMX_OK;
 }
 

@@ -176,6 +176,11 @@ def _load():
         C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
         C.POINTER(C.c_uint32),
     ]
+    lib.gemx_fold_split_stats.restype = C.c_int
+    lib.gemx_fold_split_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+        C.POINTER(C.c_uint64),
+    ]
     lib.gemx_bool_stats.restype = C.c_int
     lib.gemx_bool_stats.argtypes = [
         C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -669,6 +674,20 @@ class Shard:
         _check(self._lib.gemx_fold_stats(self._h, C.byref(f), C.byref(n),
                                          C.byref(r)), self._lib)
         return dict(folded=f.value, scanned=n.value, redone=bool(r.value))
+
+    def fold_split_stats(self):
+        """Row split of the folded waves in the last grouped query:
+        dict(k_max=<most runs a folding wave was cut into; 1 = unsplit,
+        0 = nothing folded>, tasks=<wave-tasks launched>,
+        skipped_rows=<records decoded from a checkpoint up to a run's first
+        row, summed over tasks>)."""
+        k = C.c_uint32(0)
+        t = C.c_uint32(0)
+        sk = C.c_uint64(0)
+        _check(self._lib.gemx_fold_split_stats(self._h, C.byref(k),
+                                               C.byref(t), C.byref(sk)),
+               self._lib)
+        return dict(k_max=k.value, tasks=t.value, skipped_rows=sk.value)
 
     def bool_stats(self):
         """Routing of the last aggregate scan on a boolean shard:
