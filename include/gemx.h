@@ -141,7 +141,11 @@ int gemx_shard_close(gemx_shard *);
  * engine/executor/schema.go:376-388) in one fused pass.
  * interval==0 ⇒ single window [start_time, end_time+1).
  * Rows are returned grouped by sid (descriptor order), windows ascending.
- * stats may be NULL. */
+ * stats may be NULL.
+ * Time arithmetic is int64 throughout (times below 2^62). Refused with
+ * GEMX_E_INVALID, here and in every scan_agg_* variant: interval < 0,
+ * |offset| > 2^61, and more than 1e9 windows across the part of
+ * [start_time, end_time] that holds data. */
 int gemx_scan_agg(gemx_shard *, int64_t start_time, int64_t end_time,
                   int64_t interval, int64_t offset, gemx_agg_row *out_host,
                   uint64_t cap, uint64_t *n_out, gemx_query_stats *stats);

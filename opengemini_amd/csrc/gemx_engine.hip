@@ -4433,7 +4433,9 @@ __global__ void __launch_bounds__(256) k_rate_merge(
           out.value = sqrt(acc.prev_v / (double)acc.count);
         else
           out.value = acc.first_v;
-        out.isnil = 0;
+        /* deriv/predict_linear over a single point emit nothing
+         * (linearMergeFunc: pointCount <= 1) */
+        out.isnil = lin_nil ? 1 : 0;
       }
       if (out.isnil) __hip_atomic_fetch_add(&err->gaps, 1ull, __ATOMIC_RELAXED,
                             __HIP_MEMORY_SCOPE_SYSTEM);
@@ -4676,6 +4678,7 @@ struct gemx_shard {
    * legal input and are never folded */
   std::vector<char> ser_disjoint;
   bool fold_disabled = false; /* GEMX_DISABLE_FOLD at attach */
+  bool no_gork = false;       /* GEMX_DISABLE_GORK at attach */
   bool fold_underfilled = false; /* GEMX_FOLD_UNDERFILLED at attach: fold
       even where the sub-segment split would run (measured slower there;
       an A/B and test switch) */
@@ -5578,6 +5581,7 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
   }
 
   s->fold_disabled = getenv("GEMX_DISABLE_FOLD") != nullptr;
+  s->no_gork = getenv("GEMX_DISABLE_GORK") != nullptr;
   s->fold_underfilled = getenv("GEMX_FOLD_UNDERFILLED") != nullptr;
   if (const char *fs = getenv("GEMX_FOLD_SPLIT")) {
     const long k = strtol(fs, nullptr, 10);
@@ -5784,6 +5788,26 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
                      const uint64_t *xbase = nullptr, int keep_empty = 0,
                      int redo_slot = -1) {
   if (!s) return GEMX_E_INVALID;
+  /* the validation win_start_of relies on: window ordinals are int64, but
+   * per-segment and per-series window counts are 32-bit and t - offset
+   * must not wrap (times stay below 2^62) */
+  if (interval < 0) {
+    seterr("scan_agg: interval must be >= 0");
+    return GEMX_E_INVALID;
+  }
+  if (offset > (1ll << 61) || offset < -(1ll << 61)) {
+    seterr("scan_agg: offset out of range (|offset| <= 2^61)");
+    return GEMX_E_INVALID;
+  }
+  if (interval > 0 && s->nsegs) {
+    /* the part of the query range that holds data bounds the window count */
+    const double lo = (double)std::max(start_time, s->shard_min_t);
+    const double hi = (double)std::min(end_time, s->shard_max_t);
+    if (hi > lo && (hi - lo) / (double)interval > 1e9) {
+      seterr("scan_agg: more than 1e9 windows in the query range");
+      return GEMX_E_INVALID;
+    }
+  }
   /* redo_slot >= 0: unfolded redo from scan_deliver — reuses the finished
    * slot and may run while the other slot is still in flight */
   if (async_begin && (tagq || skip_series)) {
@@ -6031,11 +6055,16 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     {
       int64_t W0 = INT64_MAX, W1 = INT64_MIN;
       for (auto &g : P.sq) {
+        /* a series with no window in the query (out of range, or masked
+         * out) carries the placeholder w_min 0: counting it would stretch
+         * the range from ordinal 0 to the data's, ~3e7 windows of 60 s at
+         * 2023 timestamps */
+        if (g.n_wins == 0) continue;
         W0 = std::min(W0, g.w_min);
         W1 = std::max(W1, g.w_min + (int64_t)g.n_wins - 1);
       }
-      P.W0 = P.sq.empty() ? 0 : W0;
-      P.n_gwins = P.sq.empty() ? 0 : (uint64_t)(W1 - W0 + 1);
+      P.W0 = (W0 == INT64_MAX) ? 0 : W0;
+      P.n_gwins = (W0 == INT64_MAX) ? 0 : (uint64_t)(W1 - W0 + 1);
       for (int sl = 0; sl < 2; sl++)
         HIP_CHECK(hipMalloc(&P.d_grows2[sl],
                             sizeof(gemx_agg_row) * (P.n_gwins ? P.n_gwins : 1)));
@@ -6276,8 +6305,9 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
    * instantiation */
   const bool use_grid = (interval != 0) && (filter_op == 0);
   /* A/B escape hatch for profiling: route gorilla segments through the
-   * generic grid kernel instead of k_scan_grid_gor */
-  static const bool no_gork = getenv("GEMX_DISABLE_GORK") != nullptr;
+   * generic grid kernel instead of k_scan_grid_gor (read at attach, like
+   * the fold switches, so one process can hold shards of both kinds) */
+  const bool no_gork = s->no_gork;
   /* wave fold is a launch-time decision on a shared plan */
   const bool fold = group_all && !tagq && use_grid && !no_gork &&
                     P.n_fold_waves > 0 && !P.fold_off;

@@ -98,6 +98,7 @@ GEMX_SEL_TOP = 0
 GEMX_SEL_BOTTOM = 1
 GEMX_TOPN_MAX = 16
 GEMX_DISTINCT_MAX = 2048
+MAX_WINDOWS = 10**9  # windows one query may span over the shard's data
 GEMX_E_UNSUPPORTED = -4
 GEMX_E_CAP = -6
 TOPN_SELS = {"top": GEMX_SEL_TOP, "bottom": GEMX_SEL_BOTTOM}
@@ -514,6 +515,18 @@ class Shard:
         key = (interval, offset, grouped)
         if key in self._bound_cache:
             return self._bound_cache[key]
+        if interval < 0:
+            raise GemxError("interval must be >= 0")
+        if interval and len(self._descs):
+            # the engine's stated limit: refuse here, before a
+            # buffer for that many rows is sized
+            span = int(self._descs["max_time"].max()) - int(
+                self._descs["min_time"].min())
+            if span // interval > MAX_WINDOWS:
+                raise GemxError(
+                    "more than 1e9 windows between the shard's first and "
+                    "last time: interval too small (pass out_cap to query "
+                    "a narrow range of it)")
         r = self._rows_bound_compute(interval, offset, grouped)
         self._bound_cache[key] = r
         return r
