@@ -221,134 +221,88 @@ struct GorDesc {
   int64_t t0, dt;      /* const-delta time (timestamp.go:190) */
 };
 
-#ifndef GEMX_GOR_BATCH_REFILL
-#define GEMX_GOR_BATCH_REFILL 0
-#endif
-#if GEMX_GOR_BATCH_REFILL
-struct GorA {
-  const uint64_t *pR;
-  uint64_t w0, w1, w2, w3;
-  uint64_t R0, R1, R2, R3, R4, R5, R6, R7; /* batch queue: 8 loads per
-                              per-lane refill event, one amortized
-                              latency per batch */
-  int fidx;
-  int bp;
-  __device__ __forceinline__ void refill() {
-    R0 = pR[0 * 64];
-    R1 = pR[1 * 64];
-    R2 = pR[2 * 64];
-    R3 = pR[3 * 64];
-    R4 = pR[4 * 64];
-    R5 = pR[5 * 64];
-    R6 = pR[6 * 64];
-    R7 = pR[7 * 64];
-    pR += 8 * 64;
-    fidx = 0;
-  }
-  __device__ __forceinline__ uint64_t pull() {
-    if (__builtin_expect(fidx >= 8, 0)) refill();
-    uint64_t lo01 = (fidx & 1) ? R1 : R0;
-    uint64_t lo23 = (fidx & 1) ? R3 : R2;
-    uint64_t hi45 = (fidx & 1) ? R5 : R4;
-    uint64_t hi67 = (fidx & 1) ? R7 : R6;
-    uint64_t lo = (fidx & 2) ? lo23 : lo01;
-    uint64_t hi = (fidx & 2) ? hi67 : hi45;
-    uint64_t v = (fidx & 4) ? hi : lo;
-    fidx++;
-    return v;
-  }
-  __device__ __forceinline__ void init(const uint64_t *arena, uint64_t base) {
-    pR = arena + base;
-    w0 = pR[0 * 64];
-    w1 = pR[1 * 64];
-    w2 = pR[2 * 64];
-    w3 = pR[3 * 64];
-    pR += 4 * 64;
-    refill();
-    bp = 0;
-  }
-  __device__ __forceinline__ void step(uint32_t adv) {
-    if (__builtin_expect(adv >= 2, 0)) {
-      w0 = w2;
-      w1 = w3;
-      w2 = pull();
-      w3 = pull();
-    } else if (adv) {
-      w0 = w1;
-      w1 = w2;
-      w2 = w3;
-      w3 = pull();
-    }
-  }
-  static __device__ __forceinline__ uint64_t fun(uint64_t a, uint64_t b,
-                                                 int bp) {
-    return (a << bp) | ((b >> (63 - bp)) >> 1);
-  }
-};
-#else
 struct GorA {
   const uint64_t *p;      /* arena cursor: word k of this stream lives at
-                             base + 64*k (u64 units, 512-byte stride). No
-                             bounds checks: the arena pad
+                             base + 64*k (u64 units, 512-byte stride); p is
+                             the address of the word in flight (M), four
+                             words past w0. No bounds checks: the arena pad
                              (GEMX_ARENA_PAD_WORDS) covers the maximum
                              possible overshoot of a corrupt stream, whose
                              garbage decode is then caught by the
                              terminator check. */
   uint64_t w0, w1, w2, w3; /* 256-bit window, bit cursor bp inside w0:
                               any <=77-bit record at bp<=63 needs <=140
-                              bits = always inside w0..w2; w3+L+M are the
-                              refill pipeline */
-  uint64_t L, M;           /* 2-deep load pipeline (an 8-register batch
-                              refill and an LDS-DMA cache warmer both
-                              measured slower — r2 notes in DESIGN.md) */
-  int bp;                  /* 0..63 */
+                              bits = always inside w0..w2 */
+  uint64_t M;              /* the one load in flight: issued by settle(),
+                              first read by the next settle() (a second
+                              staged word, an 8-register batch refill and
+                              an LDS-DMA cache warmer all measured slower
+                              or no faster — DESIGN.md §5 r2 notes and
+                              note 8) */
+  uint32_t np;             /* bit cursor relative to w0. Settled: 0..63.
+                              After advance(): up to 140, i.e. the window
+                              still owes a rotation by np >> 6 words, which
+                              p already includes. */
 
-  __device__ __forceinline__ uint64_t ldw() {
-    uint64_t w = *p;
-    p += 64;
-    return w;
-  }
-  __device__ __forceinline__ void init(const uint64_t *arena, uint64_t base) {
+  __device__ __forceinline__ void init(const uint64_t *arena, uint64_t base,
+                                       uint32_t bp = 0) {
     p = arena + base;
-    w0 = ldw();
-    w1 = ldw();
-    w2 = ldw();
-    w3 = ldw();
-    L = ldw();
-    M = ldw();
-    p -= 2 * 64; /* p tracks the address OF L until L is consumed */
-    bp = 0;
+    w0 = p[0 * 64];
+    w1 = p[1 * 64];
+    w2 = p[2 * 64];
+    w3 = p[3 * 64];
+    M = p[4 * 64];
+    p += 4 * 64;
+    np = bp;
   }
-  __device__ __forceinline__ void step(uint32_t adv) {
-    if (__builtin_expect(adv >= 2, 0)) { /* rare: wide record */
-      w0 = w2;
-      w1 = w3;
-      w2 = L;
-      w3 = M;
-      p += 2 * 64;
-      L = ldw();
-      M = ldw();
-      p -= 2 * 64;
-    } else {
-      const int c1 = (int)adv;
-      w0 = c1 ? w1 : w0;
-      w1 = c1 ? w2 : w1;
-      w2 = c1 ? w3 : w2;
-      w3 = c1 ? L : w3;
-      L = c1 ? M : L;
-      p += c1 ? 64 : 0;
-      M = p[64];
+  /* Consume a record: move the bit cursor to nb (<= 140) and the word
+   * cursor with it (one 64-bit shift-add). The window itself is rotated by
+   * the next settle(), where its old words are dead and the predicated
+   * moves can write in place: rotating here, with the record's funnels
+   * still reading the old words, cost a register copy per word and record
+   * at the loop bottom. */
+  __device__ __forceinline__ void advance(uint32_t nb) {
+    np = nb;
+    p += (uint64_t)(nb >> 6) << 6;
+  }
+  /* Bring the window under the cursor. Hot: rotate by one word where the
+   * cursor left w0 (predicated moves) and reload M. Cold, behind a
+   * wave-uniform branch so the hot path carries no exec-mask bookkeeping:
+   * the second word of a two-word advance (a record wider than 64 bits
+   * crossing a word boundary), which also fetches the word that falls
+   * between the old M and the new one. */
+  __device__ __forceinline__ void settle() {
+    const bool c = np >= 64;
+    w0 = c ? w1 : w0;
+    w1 = c ? w2 : w1;
+    w2 = c ? w3 : w2;
+    w3 = c ? M : w3;
+    M = *p;
+    if (__builtin_expect(__any(np >= 128), 0)) {
+      const bool c2 = np >= 128;
+      const uint64_t x = *(p - 64); /* in bounds on every lane: word w3 + 1 */
+      /* keep this a second rotation of the rotated words: folded into one
+       * select over the old words, it keeps those alive past the hot
+       * moves, which then cannot write in place */
+      asm volatile("" : "+v"(w1), "+v"(w2), "+v"(w3));
+      w0 = c2 ? w1 : w0;
+      w1 = c2 ? w2 : w1;
+      w2 = c2 ? w3 : w2;
+      w3 = c2 ? x : w3;
     }
+    np &= 63;
+  }
+  /* stream word under w0, relative to the stream's first word at `base` */
+  __device__ __forceinline__ uint32_t word_idx(const uint64_t *base) const {
+    return (uint32_t)((p - base) >> 6) - 4;
   }
   /* 64 bits starting at bit bp of (a,b); bp in [0,63] — the (>>1) split
    * keeps the shift amount in range without a select */
   static __device__ __forceinline__ uint64_t fun(uint64_t a, uint64_t b,
-                                                 int bp) {
+                                                 uint32_t bp) {
     return (a << bp) | ((b >> (63 - bp)) >> 1);
   }
 };
-
-#endif
 
 /* arena tail pad, u64 units: bounds the worst-case cursor overshoot of a
  * corrupt stream — (max rows+1) records x <=2 word-advances x 64 u64
@@ -475,7 +429,7 @@ struct FloatIter {
       if (use_arena) {
         /* branchless record decode from the interleaved arena (the
          * k_scan_grid_gor record path; terminator -> exhausted) */
-        uint64_t A = GorA::fun(ga.w0, ga.w1, ga.bp);
+        uint64_t A = GorA::fun(ga.w0, ga.w1, ga.np);
         uint32_t p13 = (uint32_t)(A >> 51);
         uint32_t ctrl1 = p13 >> 12;
         uint32_t neww = ctrl1 & ((p13 >> 11) & 1);
@@ -485,7 +439,7 @@ struct FloatIter {
             neww ? (uint8_t)(mr ? (64u - ((p13 >> 6) & 0x1F) - mr) : 0u)
                  : g_trail;
         uint32_t hdr = 1 + ctrl1 + (neww ? 11u : 0u);
-        uint64_t Cc = GorA::fun(ga.w1, ga.w2, ga.bp);
+        uint64_t Cc = GorA::fun(ga.w1, ga.w2, ga.np);
         uint64_t B = (A << hdr) | (Cc >> (64 - hdr));
         uint64_t sbv = (g_mean == 64) ? B : (B >> (64 - g_mean));
         g_val ^= ctrl1 ? (sbv << (g_trail & 63)) : 0;
@@ -493,10 +447,8 @@ struct FloatIter {
           g_done = 1;
           return -1;
         }
-        uint32_t np = (uint32_t)ga.bp + hdr + (ctrl1 ? (uint32_t)g_mean : 0);
-        uint32_t adv = np >> 6;
-        ga.bp = (int)(np & 63);
-        ga.step(adv);
+        ga.advance(ga.np + hdr + (ctrl1 ? (uint32_t)g_mean : 0));
+        ga.settle(); /* this iterator keeps its window settled */
         uint64_t u = g_val;
         memcpy(out, &u, 8);
         return 0;
@@ -1328,9 +1280,10 @@ static_assert(sizeof(GorCkpt) == 16, "GorCkpt is one 16-byte load");
 /* one lane's window result inside a folded wave; times travel as row
  * indices because (t0, dt) are wave-uniform */
 struct FoldLane {
-  double sum, mn, mx, firstv, lastv;
-  uint32_t min_row, max_row;
-  uint32_t min_src, max_src, fl_src; /* series index (SegQ.series_idx) */
+  double sum, mn, mx;
+  /* min/max tie-break as one key: (row << 32) | series index
+   * (SegQ.series_idx) — earlier row first, then the smaller series */
+  uint64_t min_key, max_key;
 };
 
 __device__ __forceinline__ int64_t d_rfl64(int64_t v) {
@@ -1348,45 +1301,72 @@ __device__ __forceinline__ double d_shx_f64(double v, int m) {
 /* Fixed xor-butterfly over the wave reproducing gacc_merge's algebra for
  * aligned lanes: sum adds (fixed order, so run-to-run identical; a + b is
  * commutative, so every lane ends with the same bits); min/max compare by
- * (value, earlier row, smaller series index); first/last tie on time
- * across the wave and take the smaller series index. Lanes >= nvalid are
- * absent and never win. All 64 lanes must be active. Written as a device
- * function so other lane-per-segment kernels can reuse it. */
+ * (value, earlier row, smaller series index), the two tie-breaks packed
+ * into one 64-bit key. Lanes >= nvalid are absent and never win. All 64
+ * lanes must be active. FULL is the nvalid == 64 form without the presence
+ * predicates; only a shard's single partial wave needs the general one.
+ *
+ * first/last are not reduced here: every lane covers the same rows, so the
+ * tie on time goes to the smallest series index among the valid lanes, the
+ * same lane for every window of a wave-task (fold_fl_lane below); the
+ * caller reads that lane's first/last value per window. */
+__device__ __forceinline__ uint64_t d_shx_u64(uint64_t v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+template <bool FULL>
 __device__ __forceinline__ void fold_wave_reduce(FoldLane &a, uint32_t nvalid) {
   const uint32_t lane = threadIdx.x & 63;
-  bool lu = lane < nvalid;
+  bool lu = FULL || lane < nvalid;
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
     /* the partner holds the result of its aligned m-lane block, which is
      * live when the block's first lane is present */
-    const bool ru = ((lane ^ (uint32_t)m) & ~(uint32_t)(m - 1)) < nvalid;
+    const bool ru =
+        FULL || ((lane ^ (uint32_t)m) & ~(uint32_t)(m - 1)) < nvalid;
     const double rsum = d_shx_f64(a.sum, m);
     const double rmn = d_shx_f64(a.mn, m);
     const double rmx = d_shx_f64(a.mx, m);
-    const double rfv = d_shx_f64(a.firstv, m);
-    const double rlv = d_shx_f64(a.lastv, m);
-    const uint32_t rminr = (uint32_t)__shfl_xor((int)a.min_row, m, 64);
-    const uint32_t rmaxr = (uint32_t)__shfl_xor((int)a.max_row, m, 64);
-    const uint32_t rmins = (uint32_t)__shfl_xor((int)a.min_src, m, 64);
-    const uint32_t rmaxs = (uint32_t)__shfl_xor((int)a.max_src, m, 64);
-    const uint32_t rfls = (uint32_t)__shfl_xor((int)a.fl_src, m, 64);
-    if (ru) {
-      const bool tmin =
-          !lu || rmn < a.mn ||
-          (rmn == a.mn &&
-           (rminr < a.min_row || (rminr == a.min_row && rmins < a.min_src)));
-      const bool tmax =
-          !lu || rmx > a.mx ||
-          (rmx == a.mx &&
-           (rmaxr < a.max_row || (rmaxr == a.max_row && rmaxs < a.max_src)));
-      const bool tfl = !lu || rfls < a.fl_src;
-      a.sum = lu ? a.sum + rsum : rsum;
-      if (tmin) { a.mn = rmn; a.min_row = rminr; a.min_src = rmins; }
-      if (tmax) { a.mx = rmx; a.max_row = rmaxr; a.max_src = rmaxs; }
-      if (tfl) { a.firstv = rfv; a.lastv = rlv; a.fl_src = rfls; }
-      lu = true;
-    }
+    const uint64_t rmink = d_shx_u64(a.min_key, m);
+    const uint64_t rmaxk = d_shx_u64(a.max_key, m);
+    /* straight-line: bitwise predicates and selects, no short-circuit
+     * branches (each one is an exec-mask save/restore per stage) */
+    const bool wmin =
+        (rmn < a.mn) | ((rmn == a.mn) & (rmink < a.min_key));
+    const bool wmax =
+        (rmx > a.mx) | ((rmx == a.mx) & (rmaxk < a.max_key));
+    const bool tmin = FULL ? wmin : (ru & (!lu | wmin));
+    const bool tmax = FULL ? wmax : (ru & (!lu | wmax));
+    const double ssum = a.sum + rsum;
+    a.sum = FULL ? ssum : (ru ? (lu ? ssum : rsum) : a.sum);
+    a.mn = tmin ? rmn : a.mn;
+    a.min_key = tmin ? rmink : a.min_key;
+    a.mx = tmax ? rmx : a.mx;
+    a.max_key = tmax ? rmaxk : a.max_key;
+    lu |= ru;
   }
+}
+
+/* The lane whose first/last value a folded wave reports: the valid lane
+ * with the smallest series index. Two lanes of a folding wave never share a
+ * series (they share t0 and their series are time-disjoint), so it is
+ * unique; were it not, the lowest such lane is what the pairwise tie-break
+ * used to leave in lane 0. Wave-uniform; all 64 lanes must be active. */
+__device__ __forceinline__ uint32_t fold_fl_lane(uint32_t src, bool valid,
+                                                 uint32_t *min_src) {
+  uint32_t s = valid ? src : 0xFFFFFFFFu;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1)
+    s = min(s, (uint32_t)__shfl_xor((int)s, m, 64));
+  const uint64_t hit = __ballot(valid && src == s);
+  *min_src = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+  return (uint32_t)__builtin_ctzll(hit | (1ull << 63));
+}
+__device__ __forceinline__ double d_readlane_f64(double v, uint32_t l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), (int)l);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), (int)l);
+  return __hiloint2double(hi, lo);
 }
 
 /* ---------------- branchless Gorilla grid kernel ----------------
@@ -1427,31 +1407,49 @@ __device__ __forceinline__ void fold_wave_reduce(FoldLane &a, uint32_t nvalid) {
 /* one record, straight-line: funnel-extract the 13-bit header
  * (ctrl0+ctrl1+5 lead+6 meaningful) and the significant bits from the
  * 256-bit window, advance the bit cursor, then shift the window by
- * 0/1 words (predicated moves) with one predicated reload. The only
- * branch is the rare two-word advance (record wider than 64 bits
- * crossing a word boundary). */
+ * 0/1 words (predicated moves, in place) with one reload. The only
+ * branch is wave-uniform: the rare second word of a two-word advance
+ * (record wider than 64 bits crossing a word boundary).
+ *
+ * The meaningful-bit count travels as g_sh = 64 - mean (0..63), the right
+ * shift that isolates the significant bits: mean == 64 is then shift 0, no
+ * select. GorCkpt / GorSub keep `mean`; GOR_SH / GOR_MEAN convert. Shared
+ * by every arena-mode record loop: k_scan_grid_gor<>, k_gor_ckpt and
+ * k_scan_gor_sub. */
+#define GOR_SH(mean) (64u - (uint32_t)(mean))
+#define GOR_MEAN(sh) (64u - (sh))
+__device__ __forceinline__ void gor_next(GorA &br, uint64_t &g_val,
+                                         uint32_t &g_sh, uint32_t &g_trail) {
+  br.settle();
+  const uint64_t A = GorA::fun(br.w0, br.w1, br.np);
+  const uint32_t p13 = (uint32_t)(A >> 51);
+  const uint32_t ctrl1 = p13 >> 12;
+  const uint32_t neww = ctrl1 & ((p13 >> 11) & 1);
+  const uint32_t mr = p13 & 0x3F;
+  g_sh = neww ? ((64u - mr) & 63u) : g_sh; /* mr == 0 codes mean 64 */
+  g_trail = neww ? (mr ? (64u - ((p13 >> 6) & 0x1F) - mr) : 0u) : g_trail;
+  const uint32_t hdr = 1 + ctrl1 + (neww ? 11u : 0u);
+  const uint64_t Cc = GorA::fun(br.w1, br.w2, br.np);
+  const uint64_t B = (A << hdr) | (Cc >> (64 - hdr)); /* hdr >= 1 */
+  const uint64_t sb = B >> g_sh;
+  g_val ^= ctrl1 ? (sb << (g_trail & 63)) : 0;
+  br.advance(br.np + hdr + (ctrl1 ? GOR_MEAN(g_sh) : 0));
+}
+/* uvnan hits are counted per lane in 32 bits (a stream has at most 4097
+ * records): exactly 1, the terminator, is legal */
 #define GOR_NEXT()                                                             \
     do {                                                                       \
-      uint64_t A = GorA::fun(br.w0, br.w1, br.bp);                             \
-      uint32_t p13 = (uint32_t)(A >> 51);                                      \
-      uint32_t ctrl1 = p13 >> 12;                                              \
-      uint32_t neww = ctrl1 & ((p13 >> 11) & 1);                               \
-      uint32_t mr = p13 & 0x3F;                                                \
-      g_mean = neww ? (mr ? mr : 64u) : g_mean;                                \
-      g_trail = neww ? (mr ? (64u - ((p13 >> 6) & 0x1F) - mr) : 0u) : g_trail; \
-      uint32_t hdr = 1 + ctrl1 + (neww ? 11u : 0u);                            \
-      uint64_t Cc = GorA::fun(br.w1, br.w2, br.bp);                            \
-      uint64_t B = (A << hdr) | (Cc >> (64 - hdr)); /* hdr >= 1 */             \
-      uint64_t sb = (g_mean == 64) ? B : (B >> (64 - g_mean));                 \
-      g_val ^= ctrl1 ? (sb << (g_trail & 63)) : 0;                             \
-      bad += (uint64_t)(g_val == UVNAN);                                       \
-      uint32_t np = (uint32_t)br.bp + hdr + (ctrl1 ? g_mean : 0);              \
-      uint32_t adv = np >> 6;                                                  \
-      br.bp = (int)(np & 63);                                                  \
-      br.step(adv);                                                          \
+      gor_next(br, g_val, g_sh, g_trail);                                      \
+      bad += (uint32_t)(g_val == UVNAN);                                       \
     } while (0)
 
+/* Waves per SIMD are pinned: 4 for the folding instantiation although its
+ * 95 VGPRs would allow 5, because the row-split policy (fold_split_k) was
+ * fitted to 4096 resident wave-tasks and the fifth wave measured slower at
+ * the policy's K on the headline shard (DESIGN.md section 5 note 8); 5 for
+ * the unfolded one, where it is. */
 template <bool FOLD>
+__attribute__((amdgpu_waves_per_eu(FOLD ? 4 : 5, FOLD ? 4 : 5)))
 __global__ void __launch_bounds__(256) k_scan_grid_gor(
     const uint64_t *__restrict__ arena, uint64_t arena_words,
     const GorDesc *__restrict__ gors, const gemx_seg_desc *__restrict__ descs,
@@ -1500,14 +1498,14 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
             (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.flags);
         uint64_t g_val;
         GorA br;
-        uint32_t g_mean, g_trail;
-        uint64_t bad = 0;
+        uint32_t g_sh, g_trail;
+        uint32_t bad = 0;
         if (flags & FOLD_SUB_FIRST) {
           g_val = g.first_val;
           if (g_val == UVNAN) set_err(err, GEMX_E_DECODE); /* decode stays
               inside the arena pad; the result is discarded */
           br.init(arena, g.arena_base);
-          g_mean = 64;
+          g_sh = GOR_SH(64);
           g_trail = 0;
         } else {
           /* Resume at the checkpoint below this run's first row. The
@@ -1525,15 +1523,17 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
               ckpts[ck_base[si] +
                     (uint64_t)__builtin_amdgcn_readfirstlane((int)fw.ckpt) * 64];
           g_val = ck.g_val;
-          br.init(arena, g.arena_base + (uint64_t)ck.word_idx * 64);
-          br.bp = ck.bp;
-          g_mean = ck.mean;
+          br.init(arena, g.arena_base + (uint64_t)ck.word_idx * 64, ck.bp);
+          g_sh = GOR_SH(ck.mean);
           g_trail = ck.trail;
-          bad += (uint64_t)(g_val == UVNAN);
+          bad += (uint32_t)(g_val == UVNAN);
           for (uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)fw.skip);
                q; q--)
             GOR_NEXT();
         }
+        /* first/last come from one lane for the whole wave-task */
+        uint32_t fl_src;
+        const uint32_t fl_lane = fold_fl_lane(src, valid, &fl_src);
         uint32_t i = bt[0]; /* this run's first row */
         bool pending = false; /* value of row i not decoded yet */
         for (uint32_t k = 0; k < nw; k++, orow += n_fold) {
@@ -1546,39 +1546,43 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
           a.sum = fv;
           a.mn = fv;
           a.mx = fv;
-          a.firstv = fv;
-          a.lastv = fv;
-          a.min_row = i;
-          a.max_row = i;
+          uint32_t min_row = i, max_row = i;
           for (uint32_t r = i + 1; r < gend; r++) {
             GOR_NEXT();
             const double v = __longlong_as_double((long long)g_val);
             a.sum += v;
-            if (a.mn > v) { a.mn = v; a.min_row = r; }
-            if (a.mx < v) { a.mx = v; a.max_row = r; }
-            a.lastv = v;
+            if (a.mn > v) { a.mn = v; min_row = r; }
+            if (a.mx < v) { a.mx = v; max_row = r; }
           }
+          /* g_val still holds the window's last row */
+          const double firstv = d_readlane_f64(fv, fl_lane);
+          const double lastv = d_readlane_f64(
+              __longlong_as_double((long long)g_val), fl_lane);
           /* a NaN first value pins min/max and makes the merge tree
            * order-dependent: flag it, the host redoes the query unfolded */
           if (valid && a.mn != a.mn) atomicAdd(&err->fold_nan, 1u);
-          a.min_src = a.max_src = a.fl_src = src;
-          fold_wave_reduce(a, nvalid);
+          a.min_key = ((uint64_t)min_row << 32) | src;
+          a.max_key = ((uint64_t)max_row << 32) | src;
+          if (nvalid == 64)
+            fold_wave_reduce<true>(a, nvalid);
+          else
+            fold_wave_reduce<false>(a, nvalid);
           if ((threadIdx.x & 63) == 0) {
             GAcc o;
             o.count = (int64_t)(gend - i) * nvalid;
             o.sum.f = a.sum;
             o.minv.f = a.mn;
             o.maxv.f = a.mx;
-            o.firstv.f = a.firstv;
-            o.lastv.f = a.lastv;
-            o.min_t = t0c + (int64_t)a.min_row * dtc;
-            o.max_t = t0c + (int64_t)a.max_row * dtc;
+            o.firstv.f = firstv;
+            o.lastv.f = lastv;
+            o.min_t = t0c + (int64_t)(uint32_t)(a.min_key >> 32) * dtc;
+            o.max_t = t0c + (int64_t)(uint32_t)(a.max_key >> 32) * dtc;
             o.first_t = t0c + (int64_t)i * dtc;
             o.last_t = t0c + (int64_t)(gend - 1) * dtc;
-            o.min_src = a.min_src;
-            o.max_src = a.max_src;
-            o.first_src = a.fl_src;
-            o.last_src = a.fl_src;
+            o.min_src = (uint32_t)a.min_key;
+            o.max_src = (uint32_t)a.max_key;
+            o.first_src = fl_src;
+            o.last_src = fl_src;
             o.active = 2 | 4 | 8 | 16 | 32;
             o.used = 1;
             *orow = o;
@@ -1613,8 +1617,8 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
     GorA br;
     br.init(arena, g.arena_base);
     (void)arena_words;
-    uint32_t g_mean = 64, g_trail = 0;
-    uint64_t bad = 0; /* count of uvnan hits; exactly 1 (terminator) is legal */
+    uint32_t g_sh = GOR_SH(64), g_trail = 0;
+    uint32_t bad = 0; /* count of uvnan hits; exactly 1 (terminator) is legal */
 
     Partial *base = partials + sq.partial_base;
     for (uint32_t k = 0; k < sq.n_wins; k++) base[k].has_rows = 0;
@@ -1687,10 +1691,7 @@ __global__ void __launch_bounds__(256) k_scan_grid_gor(
  * GEMX_GOR_CKPT_ROWS rows (see GorCkpt). No validation here: the scan
  * validates every record it decodes, and a corrupt stream stays inside the
  * arena pad for the same reason the scan does. The host sized the table so
- * that entries 0 .. (rows - 1) / S of every segment exist. Records the
- * rotating reader's cursor; the batch-refill A/B build has no checkpoints
- * and folds unsplit. */
-#if !GEMX_GOR_BATCH_REFILL
+ * that entries 0 .. (rows - 1) / S of every segment exist. */
 __global__ void __launch_bounds__(256) k_gor_ckpt(
     const uint64_t *__restrict__ arena, const GorDesc *__restrict__ gors,
     const uint32_t *__restrict__ seg_ids, const uint32_t *__restrict__ seg_rows,
@@ -1707,24 +1708,21 @@ __global__ void __launch_bounds__(256) k_gor_ckpt(
   uint64_t g_val = g.first_val;
   GorA br;
   br.init(arena, g.arena_base);
-  uint32_t g_mean = 64, g_trail = 0;
-  uint64_t bad = 0;
+  uint32_t g_sh = GOR_SH(64), g_trail = 0;
   for (uint32_t c = 0;; c++, out += 64) {
     GorCkpt ck;
     ck.g_val = g_val;
-    /* p tracks the address of L, four words past w0 */
-    ck.word_idx = (uint32_t)((br.p - (arena + g.arena_base)) >> 6) - 4;
-    ck.bp = (uint8_t)br.bp;
-    ck.mean = (uint8_t)g_mean;
+    ck.word_idx = br.word_idx(arena + g.arena_base);
+    ck.bp = (uint8_t)(br.np & 63);
+    ck.mean = (uint8_t)GOR_MEAN(g_sh);
     ck.trail = (uint8_t)g_trail;
     ck._pad = 0;
     *out = ck;
     if (c == last) break;
-    for (int r = 0; r < GEMX_GOR_CKPT_ROWS; r++) GOR_NEXT();
+    for (int r = 0; r < GEMX_GOR_CKPT_ROWS; r++)
+      gor_next(br, g_val, g_sh, g_trail);
   }
-  (void)bad;
 }
-#endif
 
 #undef GOR_NEXT
 
@@ -1753,34 +1751,14 @@ __global__ void __launch_bounds__(256) k_scan_gor_sub(
     const int rows = (int)sb.rows;
     uint64_t g_val = sb.g_val;
     GorA br;
-    br.init(arena, g.arena_base + (uint64_t)sb.word_idx * 64);
-    br.bp = sb.bp;
-    uint32_t g_mean = sb.mean, g_trail = sb.trail;
-    uint64_t bad = 0;
-    (void)bad; /* host walk already validated the stream */
+    br.init(arena, g.arena_base + (uint64_t)sb.word_idx * 64, sb.bp);
+    uint32_t g_sh = GOR_SH(sb.mean), g_trail = sb.trail;
+    /* no uvnan count: the host walk already validated the stream */
 
     Partial *base = partials + sq.partial_base;
     for (uint32_t k = 0; k < sq.n_wins; k++) base[k].has_rows = 0;
 
-#define GOR_NEXT()                                                             \
-    do {                                                                       \
-      uint64_t A = GorA::fun(br.w0, br.w1, br.bp);                             \
-      uint32_t p13 = (uint32_t)(A >> 51);                                      \
-      uint32_t ctrl1 = p13 >> 12;                                              \
-      uint32_t neww = ctrl1 & ((p13 >> 11) & 1);                               \
-      uint32_t mr = p13 & 0x3F;                                                \
-      g_mean = neww ? (mr ? mr : 64u) : g_mean;                                \
-      g_trail = neww ? (mr ? (64u - ((p13 >> 6) & 0x1F) - mr) : 0u) : g_trail; \
-      uint32_t hdr = 1 + ctrl1 + (neww ? 11u : 0u);                            \
-      uint64_t Cc = GorA::fun(br.w1, br.w2, br.bp);                            \
-      uint64_t B = (A << hdr) | (Cc >> (64 - hdr));                            \
-      uint64_t sbv = (g_mean == 64) ? B : (B >> (64 - g_mean));                \
-      g_val ^= ctrl1 ? (sbv << (g_trail & 63)) : 0;                            \
-      uint32_t np = (uint32_t)br.bp + hdr + (ctrl1 ? g_mean : 0);              \
-      uint32_t adv = np >> 6;                                                  \
-      br.bp = (int)(np & 63);                                                  \
-      br.step(adv);                                                          \
-    } while (0)
+#define GOR_NEXT() gor_next(br, g_val, g_sh, g_trail)
 
     int first_pending = 1;
     int i = 0;
@@ -5060,10 +5038,6 @@ static int host_gor_walk(const uint8_t *stream, uint64_t stream_bytes,
  * entries per checkpoint, sized by the group's longest segment. Segment
  * data is immutable after attach, so this runs once per shard. */
 static int build_gor_ckpts(gemx_shard *s) {
-#if GEMX_GOR_BATCH_REFILL
-  (void)s;
-  return GEMX_OK;
-#else
   const size_t n = s->fast_gor_ids.size();
   std::vector<uint32_t> base(s->nsegs ? s->nsegs : 1, 0);
   uint64_t total = 0;
@@ -5104,7 +5078,6 @@ static int build_gor_ckpts(gemx_shard *s) {
   (void)hipFree(d_ids);
   HIP_CHECK(e);
   return GEMX_OK;
-#endif
 }
 
 static int build_gor_arena(gemx_shard *s, const uint8_t *blob) {
