@@ -266,18 +266,25 @@ struct GorA {
     p += (uint64_t)(nb >> 6) << 6;
   }
   /* Bring the window under the cursor. Hot: rotate by one word where the
-   * cursor left w0 (predicated moves) and reload M. Cold, behind a
-   * wave-uniform branch so the hot path carries no exec-mask bookkeeping:
-   * the second word of a two-word advance (a record wider than 64 bits
-   * crossing a word boundary), which also fetches the word that falls
-   * between the old M and the new one. */
+   * cursor left w0 (predicated moves) and reload M there, and only there:
+   * an exec-masked load, skipped when no lane advanced. Lanes of a wave
+   * drift apart by several words, so an unmasked reload touched ~52 cache
+   * lines per wave-load against ~17 masked, and the kernel was bound by
+   * that line rate (DESIGN.md §5 note 9). Cold, behind a wave-uniform
+   * branch: the second word of a two-word advance (a record wider than 64
+   * bits crossing a word boundary), which also fetches the word that falls
+   * between the old M and the new one.
+   * MASKED = false reloads M in every lane, for FloatIter: k_rate_scan
+   * (135+ VGPRs, 2-3 waves per SIMD) waits on latency, not on the line
+   * rate, and was 5 % slower with the exec bookkeeping (note 9). */
+  template <bool MASKED = true>
   __device__ __forceinline__ void settle() {
     const bool c = np >= 64;
     w0 = c ? w1 : w0;
     w1 = c ? w2 : w1;
     w2 = c ? w3 : w2;
     w3 = c ? M : w3;
-    M = *p;
+    if (!MASKED || c) M = *p; /* elsewhere p did not move: M holds *p */
     if (__builtin_expect(__any(np >= 128), 0)) {
       const bool c2 = np >= 128;
       const uint64_t x = *(p - 64); /* in bounds on every lane: word w3 + 1 */
@@ -448,7 +455,7 @@ struct FloatIter {
           return -1;
         }
         ga.advance(ga.np + hdr + (ctrl1 ? (uint32_t)g_mean : 0));
-        ga.settle(); /* this iterator keeps its window settled */
+        ga.settle<false>(); /* this iterator keeps its window settled */
         uint64_t u = g_val;
         memcpy(out, &u, 8);
         return 0;
