@@ -377,6 +377,29 @@ int gemx_prom_irate(gemx_shard *, int64_t start_time, int64_t end_time,
                     gemx_rate_row *out_host, uint64_t cap, uint64_t *n_out,
                     gemx_query_stats *stats);
 
+/* gemx_prom_rate / gemx_prom_irate without the open-window bound: any
+ * range/step ratio in either direction, range < step included. Same
+ * sampling grid, window [ts-range, ts], NaN drop, counter resets,
+ * extrapolation, argument checks, GEMX_E_CAP rule (cap below the
+ * (series, step) rows the plan spans) and output order as those calls;
+ * float columns only. Each segment writes one record per window edge that
+ * falls in it (at most 2 per series and step, whatever the range) and a
+ * merge joins a left-edge and a right-edge record per row, so the cost
+ * follows the number of steps, not the range. Synchronous, with a plan and
+ * buffers of their own: GEMX_E_INVALID while gemx_prom_begin queries are in
+ * flight. stats->decode_ms is the edge scan, merge_ms the merge. */
+int gemx_prom_rate_wide(gemx_shard *, int64_t start_time, int64_t end_time,
+                        int64_t range_ns, int64_t step_ns, int is_rate,
+                        int is_counter, gemx_rate_row *out_host, uint64_t cap,
+                        uint64_t *n_out, gemx_query_stats *stats);
+int gemx_prom_irate_wide(gemx_shard *, int64_t start_time, int64_t end_time,
+                         int64_t range_ns, int64_t step_ns, int is_rate,
+                         gemx_rate_row *out_host, uint64_t cap, uint64_t *n_out,
+                         gemx_query_stats *stats);
+/* last wide query: edge records the plan allocated, non-nil non-NaN points
+ * scanned. Either pointer may be NULL. */
+int gemx_prom_wide_stats(gemx_shard *, uint64_t *edge_records, uint64_t *points);
+
 /* xxx_over_time family (engine/prom_functions.go: sum_over_time:232,
  * count_over_time:222, avg_over_time:341 Kahan streaming mean,
  * min/max_over_time:300-339 NaN-aware, last_over_time:528,

@@ -4616,6 +4616,7 @@ static void free_rate_plan(RatePlan &p) {
 
 struct TopPlan; /* top/bottom selector state, gemx_topn.hpp */
 struct DistinctPlan; /* distinct() state, gemx_distinct.hpp */
+struct RateWidePlan; /* edge-record rate()/irate() state, gemx_ratewide.hpp */
 
 struct gemx_shard {
   int device;
@@ -4727,6 +4728,7 @@ struct gemx_shard {
   RatePlan rate_plan;
   TopPlan *top_plan = nullptr; /* built on the first gemx_scan_topn */
   DistinctPlan *distinct_plan = nullptr; /* built on the first gemx_scan_distinct */
+  RateWidePlan *rate_wide_plan = nullptr; /* built on the first gemx_prom_*_wide */
   /* pre-aggregation metadata (pre_aggregation.go FloatPreAgg role): one
    * whole-range aggregate row per series, computed on device once and
    * served for matchPreAgg-shaped queries whose range covers the series
@@ -5679,6 +5681,7 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
 
 static void free_top_plan(gemx_shard *s);
 static void free_distinct_plan(gemx_shard *s);
+static void free_rate_wide_plan(gemx_shard *s);
 
 extern "C" int gemx_shard_close(gemx_shard *s) {
   if (!s) return GEMX_OK;
@@ -5694,6 +5697,7 @@ extern "C" int gemx_shard_close(gemx_shard *s) {
   free_rate_plan(s->rate_plan);
   free_top_plan(s);
   free_distinct_plan(s);
+  free_rate_wide_plan(s);
   (void)hipFree(s->d_blob);
   (void)hipFree(s->d_descs);
   (void)hipFree(s->d_fast_ids);
@@ -7733,6 +7737,9 @@ extern "C" int gemx_prom_over_time(gemx_shard *s, int64_t start_time,
 /* ---------------- top(field, N) / bottom(field, N) ---------------- */
 #include "gemx_topn.hpp"
 #include "gemx_distinct.hpp"
+
+/* ---------------- rate()/irate() for any range/step ---------------- */
+#include "gemx_ratewide.hpp"
 
 /* ---------------- write side (downsample output) ---------------- */
 #include "gemx_writer.hpp"

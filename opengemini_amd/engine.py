@@ -285,6 +285,14 @@ def _load():
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_Stats),
     ]
+    lib.gemx_prom_rate_wide.restype = C.c_int
+    lib.gemx_prom_rate_wide.argtypes = lib.gemx_prom_rate.argtypes
+    lib.gemx_prom_irate_wide.restype = C.c_int
+    lib.gemx_prom_irate_wide.argtypes = lib.gemx_prom_irate.argtypes
+    lib.gemx_prom_wide_stats.restype = C.c_int
+    lib.gemx_prom_wide_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+    ]
     lib.gemx_prom_holt.restype = C.c_int
     lib.gemx_prom_holt.argtypes = [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
@@ -1075,6 +1083,60 @@ class Shard:
             points=st.points, compressed_bytes=st.compressed_bytes,
             n_rows=st.n_rows,
         )
+
+    def prom_rate_wide(self, start_time, end_time, range_ns, step_ns,
+                       is_rate=True, is_counter=True, out_cap=None):
+        """prom_rate for any range/step ratio (range < step included): the
+        edge-record path, gemx_prom_rate_wide in include/gemx.h. Same rows
+        and stats as prom_rate; the rows live in a pooled buffer of their
+        own until the next wide call."""
+        lib = self._lib
+        if out_cap is None:
+            out_cap = self._rate_cap(start_time, end_time, range_ns, step_ns)
+        out = self._pooled_out("ratewide", out_cap, RATE_ROW_DTYPE)
+        n = C.c_uint64(0)
+        st = _Stats()
+        rc = lib.gemx_prom_rate_wide(
+            self._h, start_time, end_time, range_ns, step_ns,
+            1 if is_rate else 0, 1 if is_counter else 0,
+            out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(st),
+        )
+        _check(rc, lib)
+        return out[: n.value], dict(
+            decode_ms=st.decode_ms, merge_ms=st.merge_ms, total_ms=st.total_ms,
+            points=st.points, compressed_bytes=st.compressed_bytes,
+            n_rows=st.n_rows,
+        )
+
+    def prom_irate_wide(self, start_time, end_time, range_ns, step_ns,
+                        is_rate=True, out_cap=None):
+        """prom_irate for any range/step ratio (gemx_prom_irate_wide)."""
+        lib = self._lib
+        if out_cap is None:
+            out_cap = self._rate_cap(start_time, end_time, range_ns, step_ns)
+        out = self._pooled_out("ratewide", out_cap, RATE_ROW_DTYPE)
+        n = C.c_uint64(0)
+        st = _Stats()
+        rc = lib.gemx_prom_irate_wide(
+            self._h, start_time, end_time, range_ns, step_ns,
+            1 if is_rate else 0,
+            out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(st),
+        )
+        _check(rc, lib)
+        return out[: n.value], dict(
+            decode_ms=st.decode_ms, merge_ms=st.merge_ms, total_ms=st.total_ms,
+            points=st.points, compressed_bytes=st.compressed_bytes,
+            n_rows=st.n_rows,
+        )
+
+    def prom_wide_stats(self):
+        """The last wide rate query on this shard: (edge_records the plan
+        allocated, non-nil non-NaN points scanned)."""
+        e = C.c_uint64(0)
+        p = C.c_uint64(0)
+        _check(self._lib.gemx_prom_wide_stats(self._h, C.byref(e),
+                                              C.byref(p)), self._lib)
+        return e.value, p.value
 
     def prom_linear(self, start_time, end_time, range_ns, step_ns,
                     is_predict=False, scalar=0.0, out_cap=None):
