@@ -458,6 +458,36 @@ int gemx_prom_over_time(gemx_shard *, int64_t start_time, int64_t end_time,
                         gemx_rate_row *out_host, uint64_t cap, uint64_t *n_out,
                         gemx_query_stats *stats);
 
+/* gemx_prom_over_time without the open-window bound: any range/step ratio
+ * in either direction, range < step included. func is one of
+ * GEMX_PF_SUM_OT .. GEMX_PF_RESETS_OT (2-12) or GEMX_PF_ABSENT_OT (15); any
+ * other code is GEMX_E_INVALID (deriv/predict take x relative to the sample
+ * time, quantile/mad/holt have no associative combine). Same sampling grid,
+ * closed window [ts-range, ts], nil and NaN drop, argument checks and output
+ * order as gemx_prom_over_time; GEMX_E_CAP when cap is below the
+ * (series, step) rows the plan spans; absent answers every step of every
+ * series, as the reference's sample loop does. The time axis is cut at
+ * every window edge into cells; each segment leaves one 32-byte state per
+ * cell it spans, a fold computes per-block prefix and suffix states, and a
+ * row is the combine of at most two of them, so storage and work follow the
+ * number of steps, not the range. sum/avg/stdvar/stddev combine states
+ * inside a segment as well, so they are within 1e-9 relative of the
+ * reference and not bit-exact even for single-segment windows; the other
+ * functions are exact. Synchronous, with a plan and buffers of its own:
+ * GEMX_E_INVALID while gemx_prom_begin queries are in flight. end < start +
+ * range returns 0 rows and zero stats; more than 2^31 - 1 steps are
+ * refused. stats->decode_ms is the cell scan, merge_ms everything after it
+ * on the device. */
+int gemx_prom_over_time_wide(gemx_shard *, int64_t start_time, int64_t end_time,
+                             int64_t range_ns, int64_t step_ns, int func,
+                             gemx_rate_row *out_host, uint64_t cap,
+                             uint64_t *n_out, gemx_query_stats *stats);
+/* last wide over_time query: segment cell states the plan allocated, non-nil
+ * non-NaN points scanned, rows answered from stored prefix/suffix states,
+ * rows that folded their cells directly. Any pointer may be NULL. */
+int gemx_prom_wide_ot_stats(gemx_shard *, uint64_t *cell_slots, uint64_t *points,
+                            uint64_t *rows_joined, uint64_t *rows_folded);
+
 /* top(field, N) / bottom(field, N) selector scans — the series-level
  * top/bottom calls of the aggregate cursor (engine/series_call_processor.go:
  * 56-78; heap reducers engine/series_agg_reducer.gen.go:1969-2146,

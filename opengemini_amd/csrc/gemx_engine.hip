@@ -4617,6 +4617,7 @@ static void free_rate_plan(RatePlan &p) {
 struct TopPlan; /* top/bottom selector state, gemx_topn.hpp */
 struct DistinctPlan; /* distinct() state, gemx_distinct.hpp */
 struct RateWidePlan; /* edge-record rate()/irate() state, gemx_ratewide.hpp */
+struct OtWidePlan;   /* per-cell *_over_time state, gemx_otwide.hpp */
 
 struct gemx_shard {
   int device;
@@ -4729,6 +4730,7 @@ struct gemx_shard {
   TopPlan *top_plan = nullptr; /* built on the first gemx_scan_topn */
   DistinctPlan *distinct_plan = nullptr; /* built on the first gemx_scan_distinct */
   RateWidePlan *rate_wide_plan = nullptr; /* built on the first gemx_prom_*_wide */
+  OtWidePlan *ot_wide_plan = nullptr; /* built on the first gemx_prom_over_time_wide */
   /* pre-aggregation metadata (pre_aggregation.go FloatPreAgg role): one
    * whole-range aggregate row per series, computed on device once and
    * served for matchPreAgg-shaped queries whose range covers the series
@@ -5682,6 +5684,7 @@ extern "C" int gemx_shard_attach(int device, const void *blob, uint64_t blob_byt
 static void free_top_plan(gemx_shard *s);
 static void free_distinct_plan(gemx_shard *s);
 static void free_rate_wide_plan(gemx_shard *s);
+static void free_ot_wide_plan(gemx_shard *s);
 
 extern "C" int gemx_shard_close(gemx_shard *s) {
   if (!s) return GEMX_OK;
@@ -5698,6 +5701,7 @@ extern "C" int gemx_shard_close(gemx_shard *s) {
   free_top_plan(s);
   free_distinct_plan(s);
   free_rate_wide_plan(s);
+  free_ot_wide_plan(s);
   (void)hipFree(s->d_blob);
   (void)hipFree(s->d_descs);
   (void)hipFree(s->d_fast_ids);
@@ -7740,6 +7744,9 @@ extern "C" int gemx_prom_over_time(gemx_shard *s, int64_t start_time,
 
 /* ---------------- rate()/irate() for any range/step ---------------- */
 #include "gemx_ratewide.hpp"
+
+/* ---------------- *_over_time for any range/step ---------------- */
+#include "gemx_otwide.hpp"
 
 /* ---------------- write side (downsample output) ---------------- */
 #include "gemx_writer.hpp"

@@ -293,6 +293,16 @@ def _load():
     lib.gemx_prom_wide_stats.argtypes = [
         C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
     ]
+    lib.gemx_prom_over_time_wide.restype = C.c_int
+    lib.gemx_prom_over_time_wide.argtypes = [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_Stats),
+    ]
+    lib.gemx_prom_wide_ot_stats.restype = C.c_int
+    lib.gemx_prom_wide_ot_stats.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+    ]
     lib.gemx_prom_holt.restype = C.c_int
     lib.gemx_prom_holt.argtypes = [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
@@ -1137,6 +1147,43 @@ class Shard:
         _check(self._lib.gemx_prom_wide_stats(self._h, C.byref(e),
                                               C.byref(p)), self._lib)
         return e.value, p.value
+
+    def prom_over_time_wide(self, start_time, end_time, range_ns, step_ns,
+                            func, out_cap=None):
+        """prom_over_time for any range/step ratio (range < step included):
+        the per-cell path, gemx_prom_over_time_wide in include/gemx.h. func
+        is a name of OT_FUNCS; same rows and stats as prom_over_time, except
+        that absent answers the whole grid of every series. The rows live in
+        a pooled buffer of their own until the next wide over_time call."""
+        lib = self._lib
+        if out_cap is None:
+            nsteps = 1
+            if step_ns > 0 and end_time >= start_time + range_ns:
+                nsteps = int((end_time - (start_time + range_ns)) // step_ns) + 2
+            out_cap = nsteps * self._sid_count() + 16
+        code = OT_FUNCS[func] if isinstance(func, str) else int(func)
+        out = self._pooled_out("otwide", out_cap, RATE_ROW_DTYPE)
+        n = C.c_uint64(0)
+        st = _Stats()
+        rc = lib.gemx_prom_over_time_wide(
+            self._h, start_time, end_time, range_ns, step_ns, code,
+            out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(st),
+        )
+        _check(rc, lib)
+        return out[: n.value], dict(
+            decode_ms=st.decode_ms, merge_ms=st.merge_ms, total_ms=st.total_ms,
+            points=st.points, compressed_bytes=st.compressed_bytes,
+            n_rows=st.n_rows,
+        )
+
+    def prom_wide_ot_stats(self):
+        """The last wide over_time query on this shard: (cell_slots the plan
+        allocated, non-nil non-NaN points scanned, rows answered from stored
+        prefix/suffix states, rows that folded their cells directly)."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(self._lib.gemx_prom_wide_ot_stats(
+            self._h, *[C.byref(x) for x in v]), self._lib)
+        return tuple(x.value for x in v)
 
     def prom_linear(self, start_time, end_time, range_ns, step_ns,
                     is_predict=False, scalar=0.0, out_cap=None):
