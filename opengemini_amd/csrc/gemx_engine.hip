@@ -35,6 +35,7 @@
 #include <vector>
 #include <map>
 #include <tuple>
+#include <type_traits>
 #include <string>
 #include <algorithm>
 #include <chrono>
@@ -65,6 +66,16 @@ __device__ __forceinline__ double d_f64le(const uint8_t *p) {
   double d;
   memcpy(&d, p, 8);
   return d;
+}
+__device__ __forceinline__ double d_bits_f(int64_t b) {
+  double x;
+  memcpy(&x, &b, 8);
+  return x;
+}
+__device__ __forceinline__ int64_t d_f_bits(double x) {
+  int64_t b;
+  memcpy(&b, &x, 8);
+  return b;
 }
 __device__ __forceinline__ int64_t d_zigzag_dec(uint64_t u) {
   return (int64_t)((u >> 1) ^ (uint64_t)((int64_t)((u & 1) << 63) >> 63));
@@ -915,6 +926,15 @@ __device__ __forceinline__ void set_err(DevErr *e, int code) {
   atomicCAS(&e->code, 0, code);
 }
 
+/* ---------------- segment decode (shared by the per-segment scans) ------ */
+
+__device__ int64_t d_snappy_decode(const uint8_t *src, int64_t len,
+                                   uint8_t *dst, int64_t cap);
+__device__ int d_bool_decode(const uint8_t *enc, int64_t enc_len,
+                             int64_t *vbuf);
+
+#include "gemx_segdecode.hpp"
+
 /* cross-series group accumulator (semantics documented at gacc_merge) */
 struct GAcc {
   int64_t count;
@@ -975,48 +995,16 @@ __global__ void __launch_bounds__(256) k_scan_fast(
     const SegQ sq = segq[si];
     if (sq.n_wins == 0) continue; /* segment outside the query range */
 
-    /* time segment: [BlockIntegerFull][rows u32][Time enc] or
-     * [BlockIntegerOne][8B raw LE] (chunkdata_builder.go:91-95) */
-    TimeIter ti;
-    {
-      const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) { /* BlockIntegerOne */
-        ti.kind = 1;
-        ti.cur = (int64_t)d_u64le(tseg + 1);
-        ti.delta = 0;
-        ti.left = 1;
-      } else if (tseg[0] == 32 && d.time_size > 5) {
-        if (ti.init(tseg + 5, d.time_size - 5)) {
-          set_err(err, GEMX_E_DECODE);
-          return;
-        }
-      } else {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-    }
-    SegHeader h;
-    if (parse_data_header(blob + d.data_offset, d.data_size, COLTYPE, &h)) {
-      set_err(err, GEMX_E_DECODE);
+    /* streaming open from the blob (this kernel takes no arena) */
+    SegStream<COLTYPE> rd;
+    if (int rc = rd.open(blob, nullptr, nullptr, si, d)) {
+      set_err(err, rc);
       return;
     }
+    const SegHeader &h = rd.h;
+    TimeIter &ti = rd.ti;
+    auto &vit = rd.vit;
     int rows = (int)d.rows;
-
-    FloatIter fit;
-    IntIter iit;
-    int vrc;
-    if (h.one_value) {
-      /* single raw value; synthesize below */
-      vrc = 0;
-    } else if (COLTYPE == GEMX_TYPE_FLOAT) {
-      vrc = fit.init(h.enc, h.enc_len);
-    } else {
-      vrc = iit.init(h.enc, h.enc_len);
-    }
-    if (vrc) {
-      set_err(err, vrc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE);
-      return;
-    }
 
     /* running group state (one window at a time; rows time-ascending).
      * Window membership by range compare — the i64 floored division runs
@@ -1037,12 +1025,10 @@ __global__ void __launch_bounds__(256) k_scan_fast(
     int64_t min_t = 0, max_t = 0, first_t = 0, last_t = 0, grp_start_t = 0;
     Partial *base = partials + sq.partial_base;
 
-    /* const-delta timestamps (the regular-grid case, timestamp.go:190):
-     * closed form, no per-row iterator dispatch */
-    const int t_const = (ti.kind == 1);
-    const int64_t t0c = t_const ? ti.cur : 0;
-    const int64_t dtc = t_const ? ti.delta : 0;
-    if (t_const && ti.left < rows) { set_err(err, GEMX_E_DECODE); return; }
+    /* const-delta timestamps: the reader's closed form */
+    const int t_const = rd.t_const;
+    const int64_t t0c = rd.t0c;
+    const int64_t dtc = rd.dtc;
 
 #define GEMX_DECODE_ONE(fv, iv)                                                   \
       do {                                                                         \
@@ -1051,10 +1037,10 @@ __global__ void __launch_bounds__(256) k_scan_fast(
             fv = d_f64le(h.enc);                                                   \
           else                                                                     \
             memcpy(&iv, h.enc, 8);                                                 \
-        } else if (COLTYPE == GEMX_TYPE_FLOAT) {                                   \
-          if (fit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }              \
+        } else if constexpr (COLTYPE == GEMX_TYPE_FLOAT) {                         \
+          if (vit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }              \
         } else {                                                                   \
-          if (iit.next(&iv)) { set_err(err, GEMX_E_DECODE); return; }              \
+          if (vit.next(&iv)) { set_err(err, GEMX_E_DECODE); return; }              \
         }                                                                          \
       } while (0)
 
@@ -1147,16 +1133,7 @@ __global__ void __launch_bounds__(256) k_scan_fast(
       }
       double fv = 0;
       int64_t iv = 0;
-      if (h.one_value) {
-        if (COLTYPE == GEMX_TYPE_FLOAT)
-          fv = d_f64le(h.enc);
-        else
-          memcpy(&iv, h.enc, 8);
-      } else if (COLTYPE == GEMX_TYPE_FLOAT) {
-        if (fit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }
-      } else {
-        if (iit.next(&iv)) { set_err(err, GEMX_E_DECODE); return; }
-      }
+      GEMX_DECODE_ONE(fv, iv);
 
       if (FILT &&
           !d_filt_pass(COLTYPE, filter_op, filter_f, filter_i, fv, iv))
@@ -1924,7 +1901,7 @@ __global__ void __launch_bounds__(256) k_scan_grid_s8b(
     int64_t t0c, dtc;
     {
       const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) {
+      if (seg_time_is_one(tseg)) {
         t0c = (int64_t)d_u64le(tseg + 1);
         dtc = 0;
       } else {
@@ -2087,7 +2064,7 @@ __global__ void __launch_bounds__(256) k_scan_bool_grid(
     int64_t t0c, dtc;
     {
       const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) {
+      if (seg_time_is_one(tseg)) {
         t0c = (int64_t)d_u64le(tseg + 1);
         dtc = 0;
       } else {
@@ -2363,16 +2340,6 @@ __global__ void __launch_bounds__(256) k_scan_raw_lane(
   }
 }
 
-/* cross-field predicate evaluation (config #3: binaryfilterfunc compare
- * kernels, lib/binaryfilterfunc/eval_generator.gen.go:31+, applied as
- * FilterByField over a condition on a DIFFERENT field): one lane per
- * segment of the FILTER shard decodes its values and writes one pass/
- * fail bit per row (nil rows fail, as the reference's condition
- * evaluation does). The bitmap then drives the value shard's general
- * scan. */
-__device__ int64_t d_snappy_decode(const uint8_t *src, int64_t len,
-                                   uint8_t *dst, int64_t cap);
-
 /* boolean dense block (lib/encoding/bool.go:63-96): [1<<4][count u32be]
  * [bits, MSB-first] unpacked to int64 0/1. Returns the count, -1 when the
  * header is wrong or the payload is shorter than ceil(count/8) bytes. */
@@ -2386,6 +2353,13 @@ __device__ int d_bool_decode(const uint8_t *enc, int64_t enc_len,
   return (int)cnt;
 }
 
+/* cross-field predicate evaluation (config #3: binaryfilterfunc compare
+ * kernels, lib/binaryfilterfunc/eval_generator.gen.go:31+, applied as
+ * FilterByField over a condition on a DIFFERENT field): one lane per
+ * segment of the FILTER shard decodes its values and writes one pass/
+ * fail bit per row (nil rows fail, as the reference's condition
+ * evaluation does). The bitmap then drives the value shard's general
+ * scan. Per-lane scratch: the values-only layout of gemx_segdecode.hpp. */
 template <int FCOLTYPE>
 __global__ void __launch_bounds__(256) k_eval_filter(
     const uint8_t *__restrict__ blob, const gemx_seg_desc *__restrict__ descs,
@@ -2396,86 +2370,26 @@ __global__ void __launch_bounds__(256) k_eval_filter(
   uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= nlanes) return;
   uint8_t *my = scratch + (uint64_t)gid * scratch_per_lane;
-  int64_t *vbuf = (int64_t *)my;       /* dense values: 4096 × 8 */
-  uint8_t *sbuf = my + 4096 * 8;       /* snappy scratch 40KB */
 
   for (uint32_t si = gid; si < nsegs; si += nlanes) {
     const gemx_seg_desc d = descs[si];
-    int rows = (int)d.rows;
-    if (rows > 4096) { set_err(err, GEMX_E_INVALID); return; }
-    SegHeader h;
-    if (parse_data_header(blob + d.data_offset, d.data_size, FCOLTYPE, &h)) {
-      set_err(err, GEMX_E_DECODE);
+    SegBuffered<FCOLTYPE> sb;
+    if (int rc = sb.decode_values(blob, d, (int64_t *)(my + SEGV_OFF_V),
+                                  my + SEGV_OFF_SNAPPY)) {
+      set_err(err, rc);
       return;
-    }
-    int nilcount;
-    int dense;
-    if (h.one_value) {
-      nilcount = h.nilcount;
-      dense = 1 - nilcount;
-      if (dense) {
-        if (FCOLTYPE == GEMX_TYPE_BOOL) vbuf[0] = h.enc[0] & 1; /* one byte */
-        else memcpy(&vbuf[0], h.enc, 8);
-      }
-    } else if (h.enc_len == 0) {
-      nilcount = h.nilcount;
-      dense = 0;
-    } else if (FCOLTYPE == GEMX_TYPE_BOOL) {
-      dense = d_bool_decode(h.enc, h.enc_len, vbuf);
-      if (dense < 0) { set_err(err, GEMX_E_DECODE); return; }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    } else if (FCOLTYPE == GEMX_TYPE_FLOAT) {
-      int tag = h.enc[0] >> 4;
-      if (tag == 2) {
-        int64_t dl = d_snappy_decode(h.enc + 1, h.enc_len - 1, sbuf, 4096 * 8);
-        if (dl < 0 || dl % 8) { set_err(err, GEMX_E_DECODE); return; }
-        dense = (int)(dl / 8);
-        for (int i = 0; i < dense; i++) vbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-      } else {
-        FloatIter fit;
-        int rc = fit.init(h.enc, h.enc_len);
-        if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-        dense = 0;
-        double x;
-        while (dense < 4096 && fit.next(&x) == 0) {
-          memcpy(&vbuf[dense], &x, 8);
-          dense++;
-        }
-      }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    } else {
-      IntIter iit;
-      int rc = iit.init(h.enc, h.enc_len);
-      if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-      dense = 0;
-      int64_t x;
-      while (dense < 4096 && iit.next(&x) == 0) {
-        vbuf[dense] = x;
-        dense++;
-      }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    }
-    if (h.bitmap && dense + nilcount != rows) {
-      set_err(err, GEMX_E_DECODE);
-      return;
-    }
-    if (!h.bitmap && nilcount == rows && rows > 0) {
-      h.bitmap = d_zero_bm;
-      h.bm_off = 0;
     }
     const uint64_t rb = row_base[si];
-    int vi = 0;
-    for (int r = 0; r < rows; r++) {
-      int valid = 1;
-      if (h.bitmap) valid = bm_valid(&h, r);
-      else if (nilcount == rows && rows > 0) valid = 0;
+    for (int r = 0; r < sb.rows; r++) {
+      int valid;
+      int64_t xi = 0;
+      if (int rc = sb.value(r, &xi, &valid)) {
+        set_err(err, rc);
+        return;
+      }
       int pass = 0;
       if (valid) {
-        double xf = 0;
-        int64_t xi = 0;
-        if (FCOLTYPE == GEMX_TYPE_FLOAT) memcpy(&xf, &vbuf[vi], 8);
-        else xi = vbuf[vi];
-        vi++;
+        const double xf = (FCOLTYPE == GEMX_TYPE_FLOAT) ? d_bits_f(xi) : 0.0;
         pass = d_filt_pass(FCOLTYPE, filter_op, filter_f, filter_i, xf, xi);
       }
       const uint64_t bit = rb + (uint64_t)r;
@@ -2571,114 +2485,28 @@ __global__ void __launch_bounds__(256) k_scan_general(
   uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= nlanes) return;
   uint8_t *my = scratch + (uint64_t)gid * scratch_per_lane;
-  int64_t *tbuf = (int64_t *)my;                   /* 4096 × 8 */
-  int64_t *vbuf = (int64_t *)(my + 4096 * 8);      /* dense values */
-  uint8_t *sbuf = my + 2 * 4096 * 8;               /* snappy scratch 40KB */
 
   for (uint32_t li = gid; li < nseg_ids; li += nlanes) {
     uint32_t si = seg_ids[li];
     const gemx_seg_desc d = descs[si];
     const SegQ sq = segq[si];
     if (sq.n_wins == 0) continue; /* segment outside the query range */
-    int rows = (int)d.rows;
-    if (rows > 4096) { set_err(err, GEMX_E_INVALID); return; }
 
-    /* ---- decode times ---- */
-    {
-      const uint8_t *tseg = blob + d.time_offset;
-      int64_t tlen = d.time_size;
-      if (tlen < 5) { set_err(err, GEMX_E_DECODE); return; }
-      const uint8_t *enc = tseg + 5;
-      int64_t elen = tlen - 5;
-      if (tseg[0] == 18) { /* BlockIntegerOne */
-        memcpy(&tbuf[0], tseg + 1, 8);
-      } else {
-        int tag = enc[0] >> 4;
-        if (tag == 3) { /* snappy: raw LE bytes (timestamp.go:274-297) */
-          if (elen < 9) { set_err(err, GEMX_E_DECODE); return; }
-          int64_t comp_len = (int64_t)d_u32be(enc + 5);
-          int64_t dl = d_snappy_decode(enc + 9, comp_len, sbuf, 4096 * 8);
-          if (dl != rows * 8) { set_err(err, GEMX_E_DECODE); return; }
-          for (int i = 0; i < rows; i++) tbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-        } else {
-          TimeIter ti;
-          int rc = ti.init(enc, elen);
-          if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-          for (int i = 0; i < rows; i++)
-            if (ti.next(&tbuf[i])) { set_err(err, GEMX_E_DECODE); return; }
-        }
-      }
-    }
-
-    /* ---- decode data (dense values + bitmap) ---- */
-    SegHeader h;
-    if (parse_data_header(blob + d.data_offset, d.data_size, COLTYPE, &h)) {
-      set_err(err, GEMX_E_DECODE);
+    /* ---- decode times + data (dense values + bitmap) into scratch; the
+     * booleans arrive as int64 0/1, so the integer reducer below applies
+     * unchanged (the boolean reducers are the same templates). The stages
+     * below compact the buffers in place and rewrite the counts. ---- */
+    SegBuffered<COLTYPE> sb;
+    if (int rc = sb.decode(blob, d, my)) {
+      set_err(err, rc);
       return;
     }
-    int nilcount;
-    int dense;
-    if (h.one_value) {
-      nilcount = h.nilcount;
-      dense = 1 - nilcount;
-      if (dense) {
-        if (COLTYPE == GEMX_TYPE_BOOL) vbuf[0] = h.enc[0] & 1; /* one byte */
-        else memcpy(&vbuf[0], h.enc, 8);
-      }
-    } else if (h.enc_len == 0) { /* empty block */
-      nilcount = h.nilcount;
-      dense = 0;
-    } else if (COLTYPE == GEMX_TYPE_BOOL) {
-      /* bit-packed booleans unpack to int64 0/1; the integer reducer below
-       * then applies unchanged (the boolean reducers are the same templates) */
-      dense = d_bool_decode(h.enc, h.enc_len, vbuf);
-      if (dense < 0) { set_err(err, GEMX_E_DECODE); return; }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    } else if (COLTYPE == GEMX_TYPE_FLOAT) {
-      int tag = h.enc[0] >> 4;
-      if (tag == 2) { /* snappy floats (compress.go:81-84,149) */
-        int64_t dl = d_snappy_decode(h.enc + 1, h.enc_len - 1, sbuf, 4096 * 8);
-        if (dl < 0 || dl % 8) { set_err(err, GEMX_E_DECODE); return; }
-        dense = (int)(dl / 8);
-        for (int i = 0; i < dense; i++) vbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-      } else {
-        FloatIter fit;
-        int rc = fit.init(h.enc, h.enc_len);
-        if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-        dense = 0;
-        double x;
-        while (dense < 4096 && fit.next(&x) == 0) {
-          memcpy(&vbuf[dense], &x, 8);
-          dense++;
-        }
-      }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    } else {
-      IntIter iit;
-      int rc = iit.init(h.enc, h.enc_len);
-      if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-      dense = 0;
-      int64_t x;
-      while (dense < 4096 && iit.next(&x) == 0) {
-        vbuf[dense] = x;
-        dense++;
-      }
-      nilcount = h.bitmap ? h.nilcount : 0;
-    }
-    if (h.bitmap == nullptr && !h.one_value && h.enc_len > 0 && dense != rows &&
-        h.nilcount == 0) {
-      set_err(err, GEMX_E_DECODE);
-      return;
-    }
-    if (h.bitmap && dense + nilcount != rows) {
-      set_err(err, GEMX_E_DECODE);
-      return;
-    }
-    if (!h.bitmap && nilcount == rows && rows > 0) {
-      /* empty block / one-value null: no bitmap bytes, all rows nil */
-      h.bitmap = d_zero_bm;
-      h.bm_off = 0;
-    }
+    int64_t *const tbuf = sb.tbuf;
+    int64_t *const vbuf = sb.vbuf;
+    SegHeader &h = sb.h;
+    int &rows = sb.rows;
+    int &dense = sb.dense;
+    int &nilcount = sb.nilcount;
 
     {
       Partial *pb0 = partials + sq.partial_base;
@@ -2688,8 +2516,8 @@ __global__ void __launch_bounds__(256) k_scan_general(
       /* cross-field predicate: keep rows whose bit is set, preserving the
        * value column's nil structure (its own scratch slice — the clip
        * stage below rebuilds into a different one) */
-      uint8_t *xnb = my + 2 * 4096 * 8 + 40960 + 512;
-      for (int k2 = 0; k2 < 512; k2++) xnb[k2] = 0;
+      uint8_t *xnb = my + SEG_OFF_XROW_BM;
+      for (int k2 = 0; k2 < (int)SEG_BM_BYTES; k2++) xnb[k2] = 0;
       const uint64_t rb = xrow_base[si];
       int w_rows = 0, w_vals = 0, vi4 = 0;
       for (int r2 = 0; r2 < rows; r2++) {
@@ -2722,8 +2550,8 @@ __global__ void __launch_bounds__(256) k_scan_general(
     if (filter_op == 0 && (d.min_time < q_start || d.max_time > q_end)) {
       /* time slicing KEEPS nil rows inside the range (record slicing,
        * immutable/location.go) — rebuild a compact bitmap in scratch */
-      uint8_t *nb = my + 2 * 4096 * 8 + 40960; /* 512B spare */
-      for (int k2 = 0; k2 < 512; k2++) nb[k2] = 0;
+      uint8_t *nb = my + SEG_OFF_CLIP_BM;
+      for (int k2 = 0; k2 < (int)SEG_BM_BYTES; k2++) nb[k2] = 0;
       int w_rows = 0, w_vals = 0, vi3 = 0;
       for (int r2 = 0; r2 < rows; r2++) {
         int valid3 = 1;
@@ -3514,17 +3342,6 @@ struct RatePartial {
   double aux0, aux1, aux2;
 };
 
-__device__ __forceinline__ double d_bits_f(int64_t b) {
-  double x;
-  memcpy(&x, &b, 8);
-  return x;
-}
-__device__ __forceinline__ int64_t d_f_bits(double x) {
-  int64_t b;
-  memcpy(&b, &x, 8);
-  return b;
-}
-
 struct RateSlot {
   int64_t ts;     /* sample time; INT64_MIN = inactive */
   int64_t ord;    /* step ordinal (global) */
@@ -3751,103 +3568,13 @@ __global__ void __launch_bounds__(256) k_rate_scan(
       ring[j].p = z;
     }
 
-    /* value/time iterators (fast: streaming; general: via scratch) */
-    TimeIter ti;
-    FloatIter fit;
-    int64_t *tbuf = nullptr;
-    double *vbuf = nullptr;
-    uint8_t *bmv = nullptr;
-    int dense = 0, nilcount = 0;
-    SegHeader h;
-
-    if (FAST) {
-      const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) {
-        ti.kind = 1;
-        ti.cur = (int64_t)d_u64le(tseg + 1);
-        ti.delta = 0;
-        ti.left = 1;
-      } else if (tseg[0] == 32 && d.time_size > 5) {
-        if (ti.init(tseg + 5, d.time_size - 5)) { set_err(err, GEMX_E_DECODE); return; }
-      } else { set_err(err, GEMX_E_DECODE); return; }
-      if (parse_data_header(blob + d.data_offset, d.data_size, GEMX_TYPE_FLOAT, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      if (!h.one_value) {
-        int vrc;
-        if ((h.enc[0] >> 4) == 3 && gors && gors[si].arena_base != ~0ull)
-          vrc = fit.init_gor_arena(arena, &gors[si]);
-        else
-          vrc = fit.init(h.enc, h.enc_len);
-        if (vrc) { set_err(err, vrc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-      }
-    } else {
-      /* general: decode into per-lane scratch (same layout as k_scan_general) */
-      uint8_t *my = scratch + (uint64_t)gid * scratch_per_lane;
-      tbuf = (int64_t *)my;
-      vbuf = (double *)(my + 4096 * 8);
-      uint8_t *sbuf = my + 2 * 4096 * 8;
-      bmv = my + 2 * 4096 * 8 + 40960;
-      {
-        const uint8_t *tseg = blob + d.time_offset;
-        int64_t tlen = d.time_size;
-        if (tlen < 5) { set_err(err, GEMX_E_DECODE); return; }
-        if (tseg[0] == 18) {
-          memcpy(&tbuf[0], tseg + 1, 8);
-        } else {
-          const uint8_t *enc = tseg + 5;
-          int64_t elen = tlen - 5;
-          int tag = enc[0] >> 4;
-          if (tag == 3) {
-            if (elen < 9) { set_err(err, GEMX_E_DECODE); return; }
-            int64_t comp_len = (int64_t)d_u32be(enc + 5);
-            int64_t dl = d_snappy_decode(enc + 9, comp_len, sbuf, 4096 * 8);
-            if (dl != rows * 8) { set_err(err, GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++) tbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-          } else {
-            TimeIter t2;
-            int rc2 = t2.init(enc, elen);
-            if (rc2) { set_err(err, rc2 == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++)
-              if (t2.next(&tbuf[i])) { set_err(err, GEMX_E_DECODE); return; }
-          }
-        }
-      }
-      if (parse_data_header(blob + d.data_offset, d.data_size, GEMX_TYPE_FLOAT, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      nilcount = 0;
-      if (h.one_value) {
-        nilcount = h.nilcount;
-        dense = 1 - nilcount;
-        if (dense) memcpy(&vbuf[0], h.enc, 8);
-      } else if (h.enc_len == 0) {
-        nilcount = h.nilcount;
-        dense = 0;
-      } else {
-        int tag = h.enc[0] >> 4;
-        if (tag == 2) {
-          int64_t dl = d_snappy_decode(h.enc + 1, h.enc_len - 1, sbuf, 4096 * 8);
-          if (dl < 0 || dl % 8) { set_err(err, GEMX_E_DECODE); return; }
-          dense = (int)(dl / 8);
-          for (int i = 0; i < dense; i++) {
-            uint64_t u = d_u64le(sbuf + i * 8);
-            memcpy(&vbuf[i], &u, 8);
-          }
-        } else {
-          FloatIter f2;
-          int rc2 = f2.init(h.enc, h.enc_len);
-          if (rc2) { set_err(err, rc2 == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-          dense = 0;
-          double x;
-          while (dense < 4096 && f2.next(&x) == 0) vbuf[dense++] = x;
-        }
-        nilcount = h.bitmap ? h.nilcount : 0;
-      }
-      /* build a validity view for the streaming loop */
-      (void)bmv;
+    /* fast: streaming reader; general: buffered into per-lane scratch */
+    SegStream<GEMX_TYPE_FLOAT> st;
+    SegBuffered<GEMX_TYPE_FLOAT> sb;
+    if (int rc = FAST ? st.open(blob, arena, gors, si, d)
+                      : sb.decode(blob, d, scratch + (uint64_t)gid * scratch_per_lane)) {
+      set_err(err, rc);
+      return;
     }
 
     int64_t first_open = rq.s0; /* smallest possibly-active ordinal */
@@ -3864,28 +3591,16 @@ __global__ void __launch_bounds__(256) k_rate_scan(
     int64_t next_hi_start =
         start_sample + rq.s0 * step_ns - range_ns; /* ts(hi_open+1)-range */
     const int64_t last_ord_seg = rq.s0 + (int64_t)rq.n_steps - 1;
-    int vIdx = 0;
-    const int t_const = FAST && (ti.kind == 1);
-    const int64_t t0c = t_const ? ti.cur : 0;
-    const int64_t dtc = t_const ? ti.delta : 0;
 
     for (int i = 0; i < rows; i++) {
-      int64_t t;
-      double fv;
+      int64_t t, bits = 0;
       int valid = 1;
-      if (FAST) {
-        if (t_const) t = t0c + (int64_t)i * dtc;
-        else if (ti.next(&t)) { set_err(err, GEMX_E_DECODE); return; }
-        if (h.one_value) {
-          fv = d_f64le(h.enc);
-        } else if (fit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }
-      } else {
-        t = tbuf[i];
-        if (h.bitmap) valid = bm_valid(&h, i);
-        else if (nilcount == rows && rows > 0) valid = 0;
-        if (valid) fv = vbuf[vIdx++];
+      if (int rc = FAST ? st.next(i, &t, &bits) : sb.row(i, &t, &bits, &valid)) {
+        set_err(err, rc);
+        return;
       }
       if (!valid) continue;
+      const double fv = d_bits_f(bits);
       if (fv != fv) continue; /* FilterRangeNANPoint */
 
       if (FUNC >= GEMX_PF_QUANTILE) {
@@ -4942,7 +4657,7 @@ static int classify_segment(const uint8_t *blob, const gemx_seg_desc &d, int col
 static int host_grid_time(const uint8_t *blob, const gemx_seg_desc &d,
                           int64_t *t0, int64_t *dt) {
   const uint8_t *tseg = blob + d.time_offset;
-  if (tseg[0] == 18) { /* BlockIntegerOne */
+  if (seg_time_is_one(tseg)) {
     *t0 = (int64_t)h_u64le(tseg + 1);
     *dt = 0;
     return 0;
@@ -5816,7 +5531,7 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
   HIP_CHECK(hipSetDevice(s->device));
   const uint64_t nsegs = s->nsegs;
   const uint64_t scratch_per_lane =
-      4096 * 8 * 2 + 40960 + 1024; /* +512 clip bitmap, +512 xfield bitmap */
+      seg_scratch_bytes(SEG_SPARE_SCAN); /* clip bitmap + xfield bitmap */
 
   QueryPlan &P = skip_series ? s->sub_plan : s->plan;
   uint64_t skip_hash = 0;
@@ -6829,7 +6544,7 @@ static int prom_rate_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
   }
   HIP_CHECK(hipSetDevice(s->device));
   const uint64_t nsegs = s->nsegs;
-  const uint64_t scratch_per_lane = 4096 * 8 * 2 + 40960 + 4096;
+  const uint64_t scratch_per_lane = seg_scratch_bytes(SEG_SPARE_PAGE);
 
   int64_t start_sample = start_time + range_ns;
   if (end_time < start_sample) {
@@ -7285,7 +7000,7 @@ static int xfield_eval_into(gemx_shard *vs, gemx_shard *fs, int filter_op,
   if (!vs->d_xscratch) {
     vs->xlanes = (uint32_t)std::min<uint64_t>(vs->nsegs, 16384);
     HIP_CHECK(hipMalloc(&vs->d_xscratch,
-                        (uint64_t)(4096 * 8 + 40960) * vs->xlanes));
+                        SEGV_SCRATCH_BYTES * vs->xlanes));
   }
   uint32_t blocks = (vs->xlanes + 255) / 256;
   if (fs->col_type == GEMX_TYPE_BOOL) {
@@ -7295,19 +7010,19 @@ static int xfield_eval_into(gemx_shard *vs, gemx_shard *fs, int filter_op,
                        dim3(256), 0, vs->stream, fs->d_blob, fs->d_descs,
                        (uint32_t)fs->nsegs, vs->d_row_base, filter_op,
                        filter_f, filter_i, bm, vs->d_xscratch,
-                       (uint64_t)(4096 * 8 + 40960), vs->xlanes, e);
+                       SEGV_SCRATCH_BYTES, vs->xlanes, e);
   } else if (fs->col_type == GEMX_TYPE_FLOAT)
     hipLaunchKernelGGL((k_eval_filter<GEMX_TYPE_FLOAT>), dim3(blocks),
                        dim3(256), 0, vs->stream, fs->d_blob, fs->d_descs,
                        (uint32_t)fs->nsegs, vs->d_row_base, filter_op,
                        filter_f, filter_i, bm, vs->d_xscratch,
-                       (uint64_t)(4096 * 8 + 40960), vs->xlanes, e);
+                       SEGV_SCRATCH_BYTES, vs->xlanes, e);
   else
     hipLaunchKernelGGL((k_eval_filter<GEMX_TYPE_INT>), dim3(blocks),
                        dim3(256), 0, vs->stream, fs->d_blob, fs->d_descs,
                        (uint32_t)fs->nsegs, vs->d_row_base, filter_op,
                        filter_f, filter_i, bm, vs->d_xscratch,
-                       (uint64_t)(4096 * 8 + 40960), vs->xlanes, e);
+                       SEGV_SCRATCH_BYTES, vs->xlanes, e);
   return GEMX_OK;
 }
 

@@ -181,101 +181,14 @@ __global__ void __launch_bounds__(256) k_rate_edges(
     RateEdgeRec *lrec = recs + wq.rec_base;
     RateEdgeRec *rrec = lrec + wq.nl;
 
-    /* value/time iterators (fast: streaming; general: via scratch) — the
-     * decode set-up of k_rate_scan */
-    TimeIter ti;
-    FloatIter fit;
-    int64_t *tbuf = nullptr;
-    double *vbuf = nullptr;
-    int dense = 0, nilcount = 0;
-    SegHeader h;
-
-    if (FAST) {
-      const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) {
-        ti.kind = 1;
-        ti.cur = (int64_t)d_u64le(tseg + 1);
-        ti.delta = 0;
-        ti.left = 1;
-      } else if (tseg[0] == 32 && d.time_size > 5) {
-        if (ti.init(tseg + 5, d.time_size - 5)) { set_err(err, GEMX_E_DECODE); return; }
-      } else { set_err(err, GEMX_E_DECODE); return; }
-      if (parse_data_header(blob + d.data_offset, d.data_size, GEMX_TYPE_FLOAT, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      if (!h.one_value) {
-        int vrc;
-        if ((h.enc[0] >> 4) == 3 && gors && gors[si].arena_base != ~0ull)
-          vrc = fit.init_gor_arena(arena, &gors[si]);
-        else
-          vrc = fit.init(h.enc, h.enc_len);
-        if (vrc) { set_err(err, vrc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-      }
-    } else {
-      /* general: decode into per-lane scratch (same layout as k_scan_general) */
-      uint8_t *my = scratch + (uint64_t)gid * scratch_per_lane;
-      tbuf = (int64_t *)my;
-      vbuf = (double *)(my + 4096 * 8);
-      uint8_t *sbuf = my + 2 * 4096 * 8;
-      if (rows > 4096) { set_err(err, GEMX_E_DECODE); return; }
-      {
-        const uint8_t *tseg = blob + d.time_offset;
-        int64_t tlen = d.time_size;
-        if (tlen < 5) { set_err(err, GEMX_E_DECODE); return; }
-        if (tseg[0] == 18) {
-          memcpy(&tbuf[0], tseg + 1, 8);
-        } else {
-          const uint8_t *enc = tseg + 5;
-          int64_t elen = tlen - 5;
-          int tag = enc[0] >> 4;
-          if (tag == 3) {
-            if (elen < 9) { set_err(err, GEMX_E_DECODE); return; }
-            int64_t comp_len = (int64_t)d_u32be(enc + 5);
-            int64_t dl = d_snappy_decode(enc + 9, comp_len, sbuf, 4096 * 8);
-            if (dl != rows * 8) { set_err(err, GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++) tbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-          } else {
-            TimeIter t2;
-            int rc2 = t2.init(enc, elen);
-            if (rc2) { set_err(err, rc2 == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++)
-              if (t2.next(&tbuf[i])) { set_err(err, GEMX_E_DECODE); return; }
-          }
-        }
-      }
-      if (parse_data_header(blob + d.data_offset, d.data_size, GEMX_TYPE_FLOAT, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      nilcount = 0;
-      if (h.one_value) {
-        nilcount = h.nilcount;
-        dense = 1 - nilcount;
-        if (dense) memcpy(&vbuf[0], h.enc, 8);
-      } else if (h.enc_len == 0) {
-        nilcount = h.nilcount;
-        dense = 0;
-      } else {
-        int tag = h.enc[0] >> 4;
-        if (tag == 2) {
-          int64_t dl = d_snappy_decode(h.enc + 1, h.enc_len - 1, sbuf, 4096 * 8);
-          if (dl < 0 || dl % 8) { set_err(err, GEMX_E_DECODE); return; }
-          dense = (int)(dl / 8);
-          for (int i = 0; i < dense; i++) {
-            uint64_t u = d_u64le(sbuf + i * 8);
-            memcpy(&vbuf[i], &u, 8);
-          }
-        } else {
-          FloatIter f2;
-          int rc2 = f2.init(h.enc, h.enc_len);
-          if (rc2) { set_err(err, rc2 == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-          dense = 0;
-          double x;
-          while (dense < 4096 && f2.next(&x) == 0) vbuf[dense++] = x;
-        }
-        nilcount = h.bitmap ? h.nilcount : 0;
-      }
+    /* fast: streaming reader; general: buffered into per-lane scratch
+     * (gemx_segdecode.hpp) */
+    SegStream<GEMX_TYPE_FLOAT> st;
+    SegBuffered<GEMX_TYPE_FLOAT> sb;
+    if (int rc = FAST ? st.open(blob, arena, gors, si, d)
+                      : sb.decode(blob, d, scratch + (uint64_t)gid * scratch_per_lane)) {
+      set_err(err, rc);
+      return;
     }
 
     /* stream state of this segment (the sh_* state of k_rate_scan) */
@@ -287,31 +200,16 @@ __global__ void __launch_bounds__(256) k_rate_edges(
     uint32_t lcur = 0, rcur = 0;
     int64_t next_L = wq.nl ? start_time + wq.l0 * step_ns : 0;
     int64_t next_R = wq.nr ? start_sample + wq.r0 * step_ns : 0;
-    int vIdx = 0;
-    const int t_const = FAST && (ti.kind == 1);
-    const int64_t t0c = t_const ? ti.cur : 0;
-    const int64_t dtc = t_const ? ti.delta : 0;
 
     for (int i = 0; i < rows; i++) {
-      int64_t t;
-      double fv;
+      int64_t t, bits = 0;
       int valid = 1;
-      if (FAST) {
-        if (t_const) t = t0c + (int64_t)i * dtc;
-        else if (ti.next(&t)) { set_err(err, GEMX_E_DECODE); return; }
-        if (h.one_value) {
-          fv = d_f64le(h.enc);
-        } else if (fit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }
-      } else {
-        t = tbuf[i];
-        if (h.bitmap) valid = bm_valid(&h, i);
-        else if (nilcount == rows && rows > 0) valid = 0;
-        if (valid) {
-          if (vIdx >= dense) { set_err(err, GEMX_E_DECODE); return; }
-          fv = vbuf[vIdx++];
-        }
+      if (int rc = FAST ? st.next(i, &t, &bits) : sb.row(i, &t, &bits, &valid)) {
+        set_err(err, rc);
+        return;
       }
       if (!valid) continue;
+      const double fv = d_bits_f(bits);
       if (fv != fv) continue; /* FilterRangeNANPoint */
 
       /* right edges this point lies beyond: the stream before it is their
@@ -744,7 +642,7 @@ static int prom_wide_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
     *n_out = 0;
     return GEMX_OK;
   }
-  const uint64_t scratch_per_lane = 4096 * 8 * 2 + 40960 + 4096;
+  const uint64_t scratch_per_lane = seg_scratch_bytes(SEG_SPARE_PAGE);
   if (!P.valid || P.start != start_time || P.end != end_time ||
       P.range_ns != range_ns || P.step_ns != step_ns) {
     int rc = rate_wide_build_plan(s, P, start_time, end_time, range_ns, step_ns,

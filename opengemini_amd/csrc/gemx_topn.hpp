@@ -174,9 +174,10 @@ struct TopList {
 /* One lane per in-range segment; lane-owned per-(segment, window) lists:
  * pcnt[slot] kept points, pitems[slot * n + rank]. No atomics on the data
  * path. FAST = 1: nil-free segments inside the query range, streaming
- * decode. FAST = 0: everything else, decoded into per-lane scratch laid
- * out as in k_scan_general (same bounds / length checks and error codes);
- * nil rows and rows outside [q_start, q_end] are skipped. */
+ * decode (SegStream, gemx_segdecode.hpp). FAST = 0: everything else,
+ * decoded into per-lane scratch (SegBuffered, which owns the layout, the
+ * bounds / length checks and the error codes); nil rows and rows outside
+ * [q_start, q_end] are skipped. */
 template <int COLTYPE, int SEL, int FAST, int K>
 __global__ void __launch_bounds__(256) k_topn_scan(
     const uint8_t *__restrict__ blob, const uint64_t *__restrict__ arena,
@@ -195,133 +196,18 @@ __global__ void __launch_bounds__(256) k_topn_scan(
     const gemx_seg_desc d = descs[si];
     const SegQ sq = segq[si];
     if (sq.n_wins == 0) continue; /* segment outside the query range */
-    int rows = (int)d.rows;
-    if (rows > 4096) { set_err(err, GEMX_E_INVALID); return; }
+    const int rows = (int)d.rows;
 
     /* clear this lane's slots: a window can hold no usable point (time
      * gaps, nils, NaNs, rows clipped by the range) */
     for (uint32_t k = 0; k < sq.n_wins; k++) pcnt[sq.partial_base + k] = 0;
 
-    TimeIter ti;
-    FloatIter fit;
-    IntIter iit;
-    int64_t *tbuf = nullptr;
-    int64_t *vbuf = nullptr;
-    int dense = 0, nilcount = 0;
-    SegHeader h;
-
-    if (FAST) {
-      const uint8_t *tseg = blob + d.time_offset;
-      if (tseg[0] == 18) { /* BlockIntegerOne */
-        ti.kind = 1;
-        ti.cur = (int64_t)d_u64le(tseg + 1);
-        ti.delta = 0;
-        ti.left = 1;
-      } else if (tseg[0] == 32 && d.time_size > 5) {
-        if (ti.init(tseg + 5, d.time_size - 5)) { set_err(err, GEMX_E_DECODE); return; }
-      } else { set_err(err, GEMX_E_DECODE); return; }
-      if (parse_data_header(blob + d.data_offset, d.data_size, COLTYPE, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      if (h.one_value) {
-        if (h.enc_len < 8) { set_err(err, GEMX_E_DECODE); return; }
-      } else {
-        int vrc;
-        if (COLTYPE == GEMX_TYPE_FLOAT) {
-          if ((h.enc[0] >> 4) == 3 && gors && gors[si].arena_base != ~0ull)
-            vrc = fit.init_gor_arena(arena, &gors[si]);
-          else
-            vrc = fit.init(h.enc, h.enc_len);
-        } else {
-          vrc = iit.init(h.enc, h.enc_len);
-        }
-        if (vrc) { set_err(err, vrc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-      }
-    } else {
-      uint8_t *my = scratch + (uint64_t)gid * scratch_per_lane;
-      tbuf = (int64_t *)my;                 /* 4096 x 8 */
-      vbuf = (int64_t *)(my + 4096 * 8);    /* dense values */
-      uint8_t *sbuf = my + 2 * 4096 * 8;    /* snappy scratch 40 KB */
-      {
-        const uint8_t *tseg = blob + d.time_offset;
-        int64_t tlen = d.time_size;
-        if (tlen < 5) { set_err(err, GEMX_E_DECODE); return; }
-        const uint8_t *enc = tseg + 5;
-        int64_t elen = tlen - 5;
-        if (tseg[0] == 18) { /* BlockIntegerOne */
-          memcpy(&tbuf[0], tseg + 1, 8);
-        } else {
-          int tag = enc[0] >> 4;
-          if (tag == 3) { /* snappy: raw LE bytes (timestamp.go:274-297) */
-            if (elen < 9) { set_err(err, GEMX_E_DECODE); return; }
-            int64_t comp_len = (int64_t)d_u32be(enc + 5);
-            int64_t dl = d_snappy_decode(enc + 9, comp_len, sbuf, 4096 * 8);
-            if (dl != rows * 8) { set_err(err, GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++) tbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-          } else {
-            TimeIter t2;
-            int rc = t2.init(enc, elen);
-            if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-            for (int i = 0; i < rows; i++)
-              if (t2.next(&tbuf[i])) { set_err(err, GEMX_E_DECODE); return; }
-          }
-        }
-      }
-      if (parse_data_header(blob + d.data_offset, d.data_size, COLTYPE, &h)) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      if (h.one_value) {
-        nilcount = h.nilcount;
-        dense = 1 - nilcount;
-        if (dense) {
-          if (h.enc_len < 8) { set_err(err, GEMX_E_DECODE); return; }
-          memcpy(&vbuf[0], h.enc, 8);
-        }
-      } else if (h.enc_len == 0) { /* empty block */
-        nilcount = h.nilcount;
-        dense = 0;
-      } else if (COLTYPE == GEMX_TYPE_FLOAT) {
-        int tag = h.enc[0] >> 4;
-        if (tag == 2) { /* snappy floats (compress.go:81-84,149) */
-          int64_t dl = d_snappy_decode(h.enc + 1, h.enc_len - 1, sbuf, 4096 * 8);
-          if (dl < 0 || dl % 8) { set_err(err, GEMX_E_DECODE); return; }
-          dense = (int)(dl / 8);
-          for (int i = 0; i < dense; i++) vbuf[i] = (int64_t)d_u64le(sbuf + i * 8);
-        } else {
-          FloatIter f2;
-          int rc = f2.init(h.enc, h.enc_len);
-          if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-          dense = 0;
-          double x;
-          while (dense < 4096 && f2.next(&x) == 0) {
-            memcpy(&vbuf[dense], &x, 8);
-            dense++;
-          }
-        }
-        nilcount = h.bitmap ? h.nilcount : 0;
-      } else {
-        IntIter i2;
-        int rc = i2.init(h.enc, h.enc_len);
-        if (rc) { set_err(err, rc == -2 ? GEMX_E_UNSUPPORTED : GEMX_E_DECODE); return; }
-        dense = 0;
-        int64_t x;
-        while (dense < 4096 && i2.next(&x) == 0) {
-          vbuf[dense] = x;
-          dense++;
-        }
-        nilcount = h.bitmap ? h.nilcount : 0;
-      }
-      if (h.bitmap == nullptr && !h.one_value && h.enc_len > 0 && dense != rows &&
-          h.nilcount == 0) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
-      if (h.bitmap && dense + nilcount != rows) {
-        set_err(err, GEMX_E_DECODE);
-        return;
-      }
+    SegStream<COLTYPE> st;
+    SegBuffered<COLTYPE> sb;
+    if (int rc = FAST ? st.open(blob, arena, gors, si, d)
+                      : sb.decode(blob, d, scratch + (uint64_t)gid * scratch_per_lane)) {
+      set_err(err, rc);
+      return;
     }
 
     /* current window by range compare; the 64-bit floored division runs
@@ -330,37 +216,17 @@ __global__ void __launch_bounds__(256) k_topn_scan(
     int64_t ws_cur = 1, we_cur = 0; /* empty range forces the first window */
     TopList<COLTYPE, SEL, K> L;
     L.clear();
-    int vIdx = 0;
-    const int t_const = FAST && (ti.kind == 1);
-    const int64_t t0c = t_const ? ti.cur : 0;
-    const int64_t dtc = t_const ? ti.delta : 0;
-    if (t_const && ti.left < rows) { set_err(err, GEMX_E_DECODE); return; }
 
     for (int i = 0; i < rows; i++) {
       int64_t t;
       int64_t xv = 0;
-      if (FAST) {
-        if (t_const) t = t0c + (int64_t)i * dtc;
-        else if (ti.next(&t)) { set_err(err, GEMX_E_DECODE); return; }
-        if (h.one_value) {
-          memcpy(&xv, h.enc, 8);
-        } else if (COLTYPE == GEMX_TYPE_FLOAT) {
-          double fv;
-          if (fit.next(&fv)) { set_err(err, GEMX_E_DECODE); return; }
-          xv = d_f_bits(fv);
-        } else {
-          if (iit.next(&xv)) { set_err(err, GEMX_E_DECODE); return; }
-        }
-      } else {
-        t = tbuf[i];
-        int valid = 1;
-        if (h.bitmap) valid = bm_valid(&h, i);
-        else if (nilcount == rows && rows > 0) valid = 0;
-        if (!valid) continue;
-        if (vIdx >= dense) { set_err(err, GEMX_E_DECODE); return; }
-        xv = vbuf[vIdx++];
-        if (t < q_start || t > q_end) continue;
+      int valid = 1;
+      if (int rc = FAST ? st.next(i, &t, &xv) : sb.row(i, &t, &xv, &valid)) {
+        set_err(err, rc);
+        return;
       }
+      if (!valid) continue;
+      if (!FAST && (t < q_start || t > q_end)) continue;
       if (COLTYPE == GEMX_TYPE_FLOAT) {
         const double fv = d_bits_f(xv);
         if (fv != fv) continue; /* NaN never selected */
@@ -738,7 +604,7 @@ static int topn_build_plan(gemx_shard *s, TopPlan &P, int64_t start_time,
 template <int COLTYPE, int SEL, int K>
 static void topn_launch(gemx_shard *s, TopPlan &P, int group_all) {
   const int TPB = 256;
-  const uint64_t scratch_per_lane = 4096 * 8 * 2 + 40960 + 1024; /* k_scan_general's */
+  const uint64_t scratch_per_lane = seg_scratch_bytes(SEG_SPARE_SCAN);
   (void)hipEventRecord(P.ev[0], s->stream);
   if (P.n_fast_q) {
     uint32_t blocks = std::min<uint32_t>((P.n_fast_q + TPB - 1) / TPB, 65535);
@@ -817,7 +683,7 @@ extern "C" int gemx_scan_topn(gemx_shard *s, int64_t start_time, int64_t end_tim
     }
   }
   HIP_CHECK(hipSetDevice(s->device));
-  const uint64_t scratch_per_lane = 4096 * 8 * 2 + 40960 + 1024;
+  const uint64_t scratch_per_lane = seg_scratch_bytes(SEG_SPARE_SCAN);
   if (!s->top_plan) s->top_plan = new TopPlan();
   TopPlan &P = *s->top_plan;
   if (!P.valid || P.start != start_time || P.end != end_time ||
