@@ -277,8 +277,8 @@ struct GorA {
     p += (uint64_t)(nb >> 6) << 6;
   }
   /* Bring the window under the cursor. Hot: rotate by one word where the
-   * cursor left w0 (predicated moves) and reload M there, and only there:
-   * an exec-masked load, skipped when no lane advanced. Lanes of a wave
+   * cursor left w0 and reload M there, and only there: moves and load sit
+   * in one exec-masked block, skipped when no lane advanced. Lanes of a wave
    * drift apart by several words, so an unmasked reload touched ~52 cache
    * lines per wave-load against ~17 masked, and the kernel was bound by
    * that line rate (DESIGN.md §5 note 9). Cold, behind a wave-uniform
@@ -291,11 +291,28 @@ struct GorA {
   template <bool MASKED = true>
   __device__ __forceinline__ void settle() {
     const bool c = np >= 64;
-    w0 = c ? w1 : w0;
-    w1 = c ? w2 : w1;
-    w2 = c ? w3 : w2;
-    w3 = c ? M : w3;
-    if (!MASKED || c) M = *p; /* elsewhere p did not move: M holds *p */
+    if constexpr (MASKED) {
+      /* rotation and reload share the load's exec mask: four register-pair
+       * moves in the lanes that advanced, nothing in the others (as selects
+       * they ran in every lane and kept a copy of the old M alive across the
+       * loop bottom; DESIGN.md §5 note 13). Elsewhere p did not move: M
+       * still holds *p. The moves are spelled out: written as plain
+       * assignments they come back as phi copies, three before the block,
+       * four in it, three behind it, and the copy of M stays. */
+      if (c) {
+        asm volatile("v_mov_b64 %0, %1\n\tv_mov_b64 %1, %2\n\t"
+                     "v_mov_b64 %2, %3\n\tv_mov_b64 %3, %4"
+                     : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3)
+                     : "v"(M));
+        M = *p;
+      }
+    } else {
+      w0 = c ? w1 : w0;
+      w1 = c ? w2 : w1;
+      w2 = c ? w3 : w2;
+      w3 = c ? M : w3;
+      M = *p;
+    }
     if (__builtin_expect(__any(np >= 128), 0)) {
       const bool c2 = np >= 128;
       const uint64_t x = *(p - 64); /* in bounds on every lane: word w3 + 1 */
@@ -2949,12 +2966,14 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
   /* associative + commutative: full ties resolved by smaller source index
    * (= the reference's first-processed-series-wins,
    *  reccord_functions.go:489 `srcVal == v && t1 <= t2 → keep`) */
+  /* values move as their 64-bit image (.i): assigned as unions, an
+   * accumulator held in registers comes back assembled byte by byte */
   if (!r->used) return;
   l->used = 1;
   l->count += r->count;
   if (r->active & 2) {
     if (!(l->active & 2)) {
-      l->sum = r->sum;
+      l->sum.i = r->sum.i;
       l->active |= 2;
     } else if (COLTYPE == GEMX_TYPE_FLOAT)
       l->sum.f += r->sum.f;
@@ -2974,7 +2993,7 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
                      (r->min_t < l->min_t ||
                       (r->min_t == l->min_t && r->min_src < l->min_src))));
     if (take) {
-      l->minv = r->minv;
+      l->minv.i = r->minv.i;
       l->min_t = r->min_t;
       l->min_src = r->min_src;
       l->active |= 4;
@@ -2993,7 +3012,7 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
                      (r->max_t < l->max_t ||
                       (r->max_t == l->max_t && r->max_src < l->max_src))));
     if (take) {
-      l->maxv = r->maxv;
+      l->maxv.i = r->maxv.i;
       l->max_t = r->max_t;
       l->max_src = r->max_src;
       l->active |= 8;
@@ -3002,7 +3021,7 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
   if (r->active & 16) {
     if (!(l->active & 16) || r->first_t < l->first_t ||
         (r->first_t == l->first_t && r->first_src < l->first_src)) {
-      l->firstv = r->firstv;
+      l->firstv.i = r->firstv.i;
       l->first_t = r->first_t;
       l->first_src = r->first_src;
       l->active |= 16;
@@ -3011,7 +3030,7 @@ __device__ __forceinline__ void gacc_merge(GAcc *l, const GAcc *r) {
   if (r->active & 32) {
     if (!(l->active & 32) || r->last_t > l->last_t ||
         (r->last_t == l->last_t && r->last_src < l->last_src)) {
-      l->lastv = r->lastv;
+      l->lastv.i = r->lastv.i;
       l->last_t = r->last_t;
       l->last_src = r->last_src;
       l->active |= 32;
@@ -3062,32 +3081,98 @@ __global__ void __launch_bounds__(256) k_group_p1(
   }
 }
 
+/* thread t's share of n entries at `e`: t, t + 256, ... ascending, merged
+ * into `a` in that order. Four entries' loads are issued before the first
+ * merge, so a thread waits one memory round trip per four entries instead
+ * of one per entry. A slot past the end reads the last entry (in bounds)
+ * and merges as unused, which gacc_merge ignores. */
+template <int COLTYPE>
+__device__ __forceinline__ void gacc_fold_entries(GAcc &a,
+                                                  const GAcc *__restrict__ e,
+                                                  uint32_t n) {
+  constexpr uint32_t B = 4;
+  for (uint32_t c = threadIdx.x; c < n; c += B * 256) {
+    GAcc r[B];
+#pragma unroll
+    for (uint32_t j = 0; j < B; j++) {
+      const uint32_t cj = c + j * 256;
+      r[j] = e[cj < n ? cj : n - 1];
+      if (cj >= n) r[j].used = 0;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < B; j++) gacc_merge<COLTYPE>(&a, &r[j]);
+  }
+}
+
+/* lane l receives lane l + s's accumulator (s < 64; a lane whose source is
+ * past the wave keeps its own, and nobody reads that lane's result) */
+__device__ __forceinline__ int64_t d_shd_i64(int64_t v, int s) {
+  const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, s, 64);
+  const uint32_t hi =
+      (uint32_t)__shfl_down((int)(uint32_t)((uint64_t)v >> 32), s, 64);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+/* field by field: copied through a dword array the struct came back
+ * assembled from bytes, some thousand instructions a level */
+__device__ __forceinline__ GAcc gacc_shfl_down(const GAcc &a, int s) {
+  GAcc r;
+  r.count = d_shd_i64(a.count, s);
+  r.sum.i = d_shd_i64(a.sum.i, s);
+  r.minv.i = d_shd_i64(a.minv.i, s);
+  r.maxv.i = d_shd_i64(a.maxv.i, s);
+  r.firstv.i = d_shd_i64(a.firstv.i, s);
+  r.lastv.i = d_shd_i64(a.lastv.i, s);
+  r.min_t = d_shd_i64(a.min_t, s);
+  r.max_t = d_shd_i64(a.max_t, s);
+  r.first_t = d_shd_i64(a.first_t, s);
+  r.last_t = d_shd_i64(a.last_t, s);
+  r.min_src = (uint32_t)__shfl_down((int)a.min_src, s, 64);
+  r.max_src = (uint32_t)__shfl_down((int)a.max_src, s, 64);
+  r.first_src = (uint32_t)__shfl_down((int)a.first_src, s, 64);
+  r.last_src = (uint32_t)__shfl_down((int)a.last_src, s, 64);
+  r.active = (uint32_t)__shfl_down((int)a.active, s, 64);
+  r.used = (uint32_t)__shfl_down((int)a.used, s, 64);
+  return r;
+}
+
+/* One block per window. The merge order is part of the result (float sums
+ * reassociate with it): thread t folds entries t, t + 256, ... of the
+ * window into a zeroed accumulator, the p1 split entries first and then the
+ * wave-fold entries; then pairs (t, t + s), s = 128 ... 1, merge the upper
+ * into the lower. Partials stay in registers: s = 128 and s = 64 pass the
+ * upper half through LDS (an area each, so two barriers), s <= 32 are
+ * shuffles inside wave 0, and thread 0 writes the row from its registers. */
 template <int COLTYPE>
 __global__ void __launch_bounds__(256) k_group_p2(
     const GAcc *__restrict__ gtmp, uint32_t split, gemx_agg_row *__restrict__ out,
     int64_t W0, uint32_t n_gwins, int64_t interval, int64_t offset,
     int64_t q_start, int keep_empty, DevErr *__restrict__ err,
     const GAcc *__restrict__ fold = nullptr, uint32_t n_fold = 0) {
-  __shared__ GAcc sh[256];
+  __shared__ GAcc sh[128 + 64];
+  const uint32_t t = threadIdx.x;
   for (uint32_t wb = blockIdx.x; wb < n_gwins; wb += gridDim.x) {
     int64_t w = W0 + (int64_t)wb;
     GAcc a;
     memset(&a, 0, sizeof(a));
-    for (uint32_t c = threadIdx.x; c < split; c += blockDim.x)
-      gacc_merge<COLTYPE>(&a, &gtmp[wb * split + c]);
+    gacc_fold_entries<COLTYPE>(a, gtmp + (uint64_t)wb * split, split);
     /* wave-fold entries of this window ([window][folded wave]; waves that
      * do not cover the window read as unused) */
-    for (uint32_t c = threadIdx.x; c < n_fold; c += blockDim.x)
-      gacc_merge<COLTYPE>(&a, &fold[(uint64_t)wb * n_fold + c]);
-    sh[threadIdx.x] = a;
+    gacc_fold_entries<COLTYPE>(a, fold + (uint64_t)wb * n_fold, n_fold);
+    if (t >= 128) sh[t - 128] = a;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < (uint32_t)s)
-        gacc_merge<COLTYPE>(&sh[threadIdx.x], &sh[threadIdx.x + s]);
-      __syncthreads();
+    if (t < 128) gacc_merge<COLTYPE>(&a, &sh[t]);
+    if (t >= 64 && t < 128) sh[128 + t - 64] = a;
+    __syncthreads();
+    if (t < 64) {
+      gacc_merge<COLTYPE>(&a, &sh[128 + t]);
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1) {
+        const GAcc r = gacc_shfl_down(a, s);
+        gacc_merge<COLTYPE>(&a, &r);
+      }
     }
-    if (threadIdx.x == 0) {
-      GAcc *g = &sh[0];
+    if (t == 0) {
+      const GAcc *g = &a;
       gemx_agg_row o;
       memset(&o, 0, sizeof(o));
       o.sid = 0;
@@ -3112,25 +3197,25 @@ __global__ void __launch_bounds__(256) k_group_p2(
         o.first_row_time = ws; /* BuildEmptyIntervalRec interval times */
         o.count = g->count;
         o.count_time = ws;
-        o.sum = g->sum;
+        o.sum.i = g->sum.i;
         o.sum_time = ws;
         o.sum_isnil = !(g->active & 2);
-        o.minv = g->minv;
+        o.minv.i = g->minv.i;
         o.min_time = g->min_t;
         o.min_isnil = !(g->active & 4);
-        o.maxv = g->maxv;
+        o.maxv.i = g->maxv.i;
         o.max_time = g->max_t;
         o.max_isnil = !(g->active & 8);
-        o.firstv = g->firstv;
+        o.firstv.i = g->firstv.i;
         o.first_time = g->first_t;
         o.first_isnil = !(g->active & 16);
-        o.lastv = g->lastv;
+        o.lastv.i = g->lastv.i;
         o.last_time = g->last_t;
         o.last_isnil = !(g->active & 32);
       }
       out[wb] = o;
     }
-    __syncthreads();
+    __syncthreads(); /* sh is reused by the next window (n_gwins > 65535) */
   }
 }
 
@@ -6367,24 +6452,30 @@ static int scan_impl(gemx_shard *s, int64_t start_time, int64_t end_time,
   }
   HIP_CHECK(hipEventRecord(ev2, s->stream));
 
-  /* hand the row fetch to the copy stream so it can overlap the NEXT
-   * query's kernels (double-buffered d_rows): copy waits on ev2, rows
-   * land straight in the caller's (pinned-registered) buffer. */
+  /* pipelined begin: hand the row fetch to the copy stream so it can
+   * overlap the NEXT query's kernels (double-buffered d_rows): copy waits
+   * on ev2, rows land straight in the caller's (pinned-registered) buffer. */
   uint64_t fetch_rows = tagq ? (uint64_t)s->tag_plan.n_groups * P.n_gwins
                              : (group_all ? P.n_gwins : total_rows);
   if (fetch_rows > cap) {
     seterr("output capacity too small");
     return GEMX_E_CAP;
   }
-  HIP_CHECK(hipStreamWaitEvent(s->copy_stream, ev2, 0));
+  /* a synchronous call waits for its own rows before it returns, so there
+   * is no next scan to overlap: it fetches on the compute stream, in order
+   * behind its kernels, and skips the cross-stream hand-over (12 µs in
+   * note 9's traced timeline; 0.011 ms/step on the default bench,
+   * DESIGN.md §5 note 13) */
+  hipStream_t fetch_stream = async_begin ? s->copy_stream : s->stream;
+  if (async_begin) HIP_CHECK(hipStreamWaitEvent(s->copy_stream, ev2, 0));
   HIP_CHECK(hipMemcpyAsync(s->h_err2[slot], d_err, sizeof(DevErr),
-                           hipMemcpyDeviceToHost, s->copy_stream));
+                           hipMemcpyDeviceToHost, fetch_stream));
   HIP_CHECK(hipMemcpyAsync(
       out_host,
       tagq ? s->tag_plan.d_rows : (group_all ? P.d_grows2[slot] : d_rows),
       sizeof(gemx_agg_row) * fetch_rows, hipMemcpyDeviceToHost,
-      s->copy_stream));
-  HIP_CHECK(hipEventRecord(s->ev_copy[slot], s->copy_stream));
+      fetch_stream));
+  HIP_CHECK(hipEventRecord(s->ev_copy[slot], fetch_stream));
 
   if (async_begin) {
     auto &pe = s->pend[(s->pend_head + s->pend_count) & 1];
